@@ -25,6 +25,8 @@ Rank 0 prints ONE JSON line of < 6 KB.  Besides the contract fields it carries
                 host cores on a bounded sample of the same workload.
 The per-kernel table of every profiled HIP kernel (`kernels`, `roofline_all`) goes to
 profiles/bench_detail_<config>_<dtype>.json (and gpurun_out/ when that exists), not to stdout.
+`--dump-outputs DIR` writes what the last timed step returned (both losses, the updated G and D
+parameters) as DIR/<name>.npy, so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -79,7 +81,46 @@ def parse():
                          "default single-GPU run appends as `bf16_configs2` after the timed region")
     ap.add_argument("--cpu-batch", type=int, default=32)
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = the reference's own setting (train.py:16: 5 threads)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller -- both losses and the "
+                         "updated G and D parameters -- as DIR/<name>.npy (rank 0; float32, at most 64 MB in all)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def snapshot_outputs(losses, G, D):
+    """Host copies of what a timed step hands its caller: the two losses and every parameter of G and D after the step's
+    AdamW updates (float32 / float64 as computed)."""
+    def host(t):
+        t = t.detach()
+        return t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+    outs = {"d_loss": host(losses[0]), "g_loss": host(losses[1])}
+    for tag, net in (("G", G), ("D", D)):
+        for name, p in net.named_parameters():
+            outs[f"{tag}.{name}"] = host(p)
+    return outs
+
+
+def dump_outputs(outs, out_dir, budget=DUMP_BUDGET_BYTES):
+    """Write every array as out_dir/<name>.npy.  Over the byte budget, each array is cut to a fixed, seeded sample of its
+    flattened elements (sorted indices; the same for every run and build) sized to its share of the budget."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    header = 128      # bytes of a .npy header (format 1.0, padded to a multiple of 64; 128 for these shapes)
+    fixed = sum(header + (v.nbytes if v.size <= 1 else 0) for v in outs.values())
+    total = sum(v.nbytes for v in outs.values() if v.size > 1)
+    room = budget - fixed
+    for name, v in outs.items():
+        if fixed + total > budget and v.size > 1:
+            keep = max(1, v.size * room // total)
+            idx = np.sort(np.random.default_rng(0).choice(v.size, size=keep, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), v)
 
 
 def _cpu_gan_step_rate(workload, batch, threads, steps=5, budget_s=60.0):
@@ -291,6 +332,8 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     _lib.prof_enable(False)
+    # the last timed step's results, taken before the untimed steps below move the parameters again
+    dumped = snapshot_outputs(losses, G, D) if args.dump_outputs and rank == 0 else None
     n_ar, ms_ar = stepper.collective_ms() if world > 1 else (0, 0.0)      # the timed steps' all-reduces only
     stepper.time_collectives(False)
     attn_stats = {k: (_lib.prof_read(k), dgf.traffic_bytes(k), dgf.traffic_floor_bytes(k)) for k in attn_kernels}
@@ -607,6 +650,8 @@ def main():
             except OSError:
                 pass
         out["detail_file"] = written
+        if dumped is not None:
+            dump_outputs(dumped, args.dump_outputs)
 
         def rnd(v):      # 6 significant digits: the line must stay under 6 KB
             if isinstance(v, float):

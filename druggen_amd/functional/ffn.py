@@ -56,7 +56,8 @@ def _ffn_packed_f32(w1, w2):
 
 def set_fused_ffn_f32(on: bool) -> None:
     """Route the float32 feed-forward FORWARD through the fused kernel (dg_ffn_ln_fwd_f32: the [R,384] hidden tensor stays on
-    chip; default) or through the two row-GEMM launches (``options.ffn_f32``; DG_FFN_F32=unfused at import)."""
+    chip; DG_FFN_F32=fused at import) or through the two row-GEMM launches (``options.ffn_f32``; default: the fused kernel's
+    results are not bit-reproducible from run to run)."""
     options.ffn_f32 = "fused" if on else "unfused"
 
 

@@ -6,7 +6,8 @@ The C library (libdruggen_hip.so) reads no environment variable at all.
 
     variable                values (first = default)        what it selects
     DG_HIDDEN               dh16 | dh24 | f32 | f24 | f16   storage of the float32 feed-forward's [R,384] hidden tensors (functional.hidden_storage)
-    DG_FFN_F32              fused | unfused                 float32 feed-forward forward as ONE kernel (hidden tensor on chip) or two row GEMMs
+    DG_FFN_F32              unfused | fused                 float32 feed-forward forward as two row GEMMs or ONE kernel (hidden tensor on
+                                                            chip; its results vary in the last bits from run to run: not the default)
     DG_ATTN_HALF_F32        fused | n48 | off               float32 fused attention-half forward: N <= 96 | N <= 48 only | three launches
     DG_ATTN_HALF_F32_BWD    fused | nograph | off | force   float32 fused attention-half backward part 1 (force: any batch size, tests)
     DG_ATTN_HALF            fused | unfused | force         bf16 fused attention half (force: also 48 < N <= 96)
@@ -26,7 +27,7 @@ import os
 
 _CHOICES = {
     "hidden": ("dh16", "dh24", "f32", "f24", "f16"),
-    "ffn_f32": ("fused", "unfused"),
+    "ffn_f32": ("unfused", "fused"),
     "attn_half_f32": ("fused", "n48", "off"),
     "attn_half_f32_bwd": ("fused", "nograph", "off", "force"),
     "attn_half": ("fused", "unfused", "force"),

@@ -1103,6 +1103,8 @@ def test_fused_float32_feed_forward_forward(R, scale):
     dy = _gen((R, C), 99).float().cuda()
     ins = [c[k] for k in ("x", "w1", "b1", "w2", "b2", "gamma", "beta")]
     got = {}
+    from druggen_amd.options import options as dg_options
+    prev_fused = dg_options.ffn_f32 == "fused"      # (the shipped choice comes back)
     try:
         for fused in (True, False):
             dgf.set_fused_ffn_f32(fused)
@@ -1111,7 +1113,7 @@ def test_fused_float32_feed_forward_forward(R, scale):
             got[fused] = dict(y=y.detach(), pre=pre.detach(), mean=mean, rstd=rstd, h=dgf.hidden_to_float(sv[7], R, H), bits=sv[11],
                               hbytes=sv[7].numel(), g=torch.autograd.grad(y, ins, dy))
     finally:
-        dgf.set_fused_ffn_f32(True)
+        dgf.set_fused_ffn_f32(prev_fused)
     a = got[True]
     assert a["hbytes"] == int(_lib().load().dg_hidden_bytes(R, H, _lib().F32_H16))      # one fp16 plane + row scales
     assert _rel(a["y"], y64) < TOL and _rel(a["pre"], pre64) < TOL
@@ -1155,6 +1157,8 @@ def test_fused_float32_feed_forward_degenerate_rows():
         ins = [case[k] for k in ("x", "w1", "b1", "w2", "b2", "gamma", "beta")]
         dy = _gen((R, C), 98).float().cuda()
         got = {}
+        from druggen_amd.options import options as dg_options
+        prev_fused = dg_options.ffn_f32 == "fused"      # (the shipped choice comes back)
         try:
             for fused in (True, False):
                 dgf.set_fused_ffn_f32(fused)
@@ -1162,7 +1166,7 @@ def test_fused_float32_feed_forward_degenerate_rows():
                 sv = y.grad_fn.saved_tensors
                 got[fused] = dict(y=y.detach(), pre=pre.detach(), h=dgf.hidden_to_float(sv[7], R, H), g=torch.autograd.grad(y, ins, dy))
         finally:
-            dgf.set_fused_ffn_f32(True)
+            dgf.set_fused_ffn_f32(prev_fused)
         a, b = got[True], got[False]
         assert all(bool(torch.isfinite(t).all()) for t in (a["y"], a["pre"], a["h"]) + tuple(a["g"]))
         rows = torch.ones(R, dtype=torch.bool)

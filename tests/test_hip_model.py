@@ -117,6 +117,8 @@ def test_c5_b2_generator_gradient_sits_on_a_relu_threshold():
     generator's logits put the G gradient of c5_b2 on either of two branches 1e-3 apart; c2_b2 has one branch."""
     from druggen_amd import functional as dgf
     dgf.set_fused_ffn_f32(False)
+    from druggen_amd.options import options as dg_options
+    prev_fused = dg_options.ffn_f32 == "fused"      # (the shipped choice comes back)
     try:
         case, fx = cases.CASES["c5_b2"], harness.load_fixture("c5_b2")
         errs = [_worst_g_grad(case, fx, seed)[0] for seed in range(1, 17)]
@@ -128,7 +130,7 @@ def test_c5_b2_generator_gradient_sits_on_a_relu_threshold():
         assert max(errs2) < TOL_GRAD, errs2
         print("c5_b2:", " ".join(f"{e:.1e}" for e in errs), "| c2_b2:", " ".join(f"{e:.1e}" for e in errs2))
     finally:
-        dgf.set_fused_ffn_f32(True)
+        dgf.set_fused_ffn_f32(prev_fused)
 
 
 def test_reference_loss_code_path_works_on_these_modules():

@@ -301,3 +301,29 @@ def test_smiles_sample_matches_oracle_densify():
     assert np.array_equal(a2, a) and np.array_equal(x2, x)
     assert [g.num_atoms for g in graphs] == [39, 29, 29, 34]
     assert (a[..., 1:].sum((1, 2, 3)) == 2 * np.array([43, 33, 32, 38])).all()      # each bond appears twice
+
+
+def test_bench_dump_outputs_writes_npy_and_samples_over_budget(tmp_path):
+    """bench.py --dump-outputs: one DIR/<name>.npy per array, float32 / float64 as computed; over the byte budget every array
+    is cut to the same seeded sample of its elements (two dumps of the same outputs are identical) and the whole stays under it."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+    outs = {"d_loss": np.array(1.5, np.float32), "g_loss": np.array(-0.25, np.float64),
+            "G.w": rng.standard_normal((300, 128)).astype(np.float32), "D.w": rng.standard_normal(5000).astype(np.float32)}
+    bench.dump_outputs(outs, str(tmp_path / "full"))
+    for k, v in outs.items():
+        got = np.load(tmp_path / "full" / f"{k}.npy")
+        assert got.dtype == v.dtype and np.array_equal(got, v), k
+    budget = 64 * 1024
+    for sub in ("a", "b"):
+        bench.dump_outputs(outs, str(tmp_path / sub), budget=budget)
+    sizes = 0
+    for k, v in outs.items():
+        a, b = (np.load(tmp_path / sub / f"{k}.npy") for sub in ("a", "b"))
+        assert np.array_equal(a, b) and a.dtype == v.dtype, k
+        assert np.isin(a, v.reshape(-1)).all(), k
+        sizes += os.path.getsize(tmp_path / "a" / f"{k}.npy")
+    assert np.load(tmp_path / "a" / "G.w.npy").size < outs["G.w"].size and sizes <= budget
