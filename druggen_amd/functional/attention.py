@@ -30,18 +30,85 @@ def _attn_shapes(q, e):
     return B, N, C
 
 
+# dg_attn_core_* hold a row's neighbours in one wave (N <= 96); dg_attn_core_long_* spread it over a workgroup (N <= 256)
+ATTN_SHORT_MAX_N = 96
+ATTN_MAX_N = 256
+
+
+def _check_neighbours(N: int) -> None:
+    if N > ATTN_MAX_N:
+        raise RuntimeError(f"graph attention: {N} neighbours (vertexes / max_atom) is above the supported maximum of "
+                           f"{ATTN_MAX_N}")
+
+
+def _long_workspace(q, B, N, C):
+    need = int(_lib.load().dg_attn_core_long_workspace_bytes(B, N, C))
+    return (_scratch(q, need, "attn_long") if need else None), need
+
+
+def _core_fwd(q, k, v, e, s, o, alpha, B, N, C):
+    """One attention-core forward launch: dg_attn_core_fwd up to 96 neighbours, dg_attn_core_long_fwd above."""
+    _check_neighbours(N)
+    lib = _lib.load()
+    fn, name = (lib.dg_attn_core_fwd, "dg_attn_core_fwd") if N <= ATTN_SHORT_MAX_N else (lib.dg_attn_core_long_fwd,
+                                                                                          "dg_attn_core_long_fwd")
+    with _dev(q):
+        _lib.check(fn(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(e), _lib.ptr(s), _lib.ptr(o), B, N, C, alpha,
+                      _lib.dt(q), _lib.stream_of(q)), name)
+    _account("attn_fwd", q.element_size() * B * ((2 if s is not None else 1) * N * N * C + 4 * N * C))
+
+
+def _core_bwd(q, k, v, e, ws, wo, add_e, dq, dk, dv, de, alpha):
+    """One first-order attention-core backward launch (dg_attn_core_bwd_add / dg_attn_core_long_bwd)."""
+    B, N, C = q.shape[0], q.shape[1], q.shape[2]
+    _check_neighbours(N)
+    lib = _lib.load()
+    extra = 0
+    with _dev(q):
+        if N <= ATTN_SHORT_MAX_N:
+            _lib.check(lib.dg_attn_core_bwd_add(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(e), _lib.ptr(ws),
+                                                _lib.ptr(wo), _lib.ptr(add_e), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv),
+                                                _lib.ptr(de), B, N, C, alpha, _lib.dt(q), _lib.stream_of(q)),
+                       "dg_attn_core_bwd")
+        else:
+            work, extra = _long_workspace(q, B, N, C)
+            wp = work.data_ptr() if extra else None
+            _lib.check(lib.dg_attn_core_long_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(e), _lib.ptr(ws),
+                                                 _lib.ptr(wo), _lib.ptr(add_e), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv),
+                                                 _lib.ptr(de), wp, extra, B, N, C, alpha, _lib.dt(q), _lib.stream_of(q)),
+                       "dg_attn_core_long_bwd")
+    base = q.element_size() * B * ((2 + (ws is not None) + (add_e is not None)) * N * N * C + 7 * N * C)
+    _account("attn_bwd", base + 2 * extra, floor=base)      # (long path: the column partials are written and read once)
+
+
+def _core_bwd2(q, k, v, e, ws, wo, tq, tk, tv, te, gq, gk, gv, ge, gws, gwo, alpha):
+    """One second-order attention-core launch (dg_attn_core_bwd2 / dg_attn_core_long_bwd2)."""
+    B, N, C = q.shape[0], q.shape[1], q.shape[2]
+    _check_neighbours(N)
+    lib = _lib.load()
+    extra = 0
+    args = [_lib.ptr(x) for x in (q, k, v, e, ws, wo, tq, tk, tv, te, gq, gk, gv, ge, gws, gwo)]
+    with _dev(q):
+        if N <= ATTN_SHORT_MAX_N:
+            _lib.check(lib.dg_attn_core_bwd2(*args, B, N, C, alpha, _lib.dt(q), _lib.stream_of(q)), "dg_attn_core_bwd2")
+        else:
+            work, extra = _long_workspace(q, B, N, C)
+            wp = work.data_ptr() if extra else None
+            _lib.check(lib.dg_attn_core_long_bwd2(*args, wp, extra, B, N, C, alpha, _lib.dt(q),
+                                                  _lib.stream_of(q)), "dg_attn_core_long_bwd2")
+    base = q.element_size() * B * ((5 if ws is not None else 3) * N * N * C + 11 * N * C)
+    _account("attn_bwd2", base + 2 * extra, floor=base)
+
+
 class _AttnCore(Function):
     @staticmethod
     def forward(ctx, q, k, v, e, alpha, need_s):
         q, k, v, e = _c(q), _c(k), _c(v), _c(e)
         B, N, C = _attn_shapes(q, e)
-        lib = _lib.load()
+        _check_neighbours(N)
         s = torch.empty_like(e) if need_s else None
         o = torch.empty_like(q)
-        with _dev(q):
-            _lib.check(lib.dg_attn_core_fwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(e), _lib.ptr(s),
-                                            _lib.ptr(o), B, N, C, alpha, _lib.dt(q), _lib.stream_of(q)), "dg_attn_core_fwd")
-        _account("attn_fwd", q.element_size() * B * ((2 if need_s else 1) * N * N * C + 4 * N * C))
+        _core_fwd(q, k, v, e, s, o, alpha, B, N, C)
         ctx.save_for_backward(q, k, v, e)
         ctx.alpha = alpha
         ctx.set_materialize_grads(False)
@@ -67,14 +134,9 @@ class _AttnCoreBwd(Function):
         B, N, C = _attn_shapes(q, e)
         ws = None if ws is None else _c(ws)
         wo = _c(wo)
-        lib = _lib.load()
         dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
         de = torch.empty_like(e)
-        with _dev(q):
-            _lib.check(lib.dg_attn_core_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(e), _lib.ptr(ws),
-                                            _lib.ptr(wo), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(de),
-                                            B, N, C, alpha, _lib.dt(q), _lib.stream_of(q)), "dg_attn_core_bwd")
-        _account("attn_bwd", q.element_size() * B * ((3 if ws is not None else 2) * N * N * C + 7 * N * C))
+        _core_bwd(q, k, v, e, ws, wo, None, dq, dk, dv, de, alpha)
         ctx.save_for_backward(q, k, v, e, ws, wo)
         ctx.alpha = alpha
         return dq, dk, dv, de
@@ -85,18 +147,11 @@ class _AttnCoreBwd(Function):
         q, k, v, e, ws, wo = ctx.saved_tensors
         B, N, C = _attn_shapes(q, e)
         tq, tk, tv, te = _c(tq), _c(tk), _c(tv), _c(te)
-        lib = _lib.load()
         gq, gk, gv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
         ge = torch.empty_like(e)
         gws = torch.empty_like(e) if ws is not None else None
         gwo = torch.empty_like(q)
-        with _dev(q):
-            _lib.check(lib.dg_attn_core_bwd2(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(e), _lib.ptr(ws),
-                                             _lib.ptr(wo), _lib.ptr(tq), _lib.ptr(tk), _lib.ptr(tv), _lib.ptr(te),
-                                             _lib.ptr(gq), _lib.ptr(gk), _lib.ptr(gv), _lib.ptr(ge), _lib.ptr(gws),
-                                             _lib.ptr(gwo), B, N, C, ctx.alpha, _lib.dt(q), _lib.stream_of(q)),
-                       "dg_attn_core_bwd2")
-        _account("attn_bwd2", q.element_size() * B * ((5 if ws is not None else 3) * N * N * C + 11 * N * C))
+        _core_bwd2(q, k, v, e, ws, wo, tq, tk, tv, te, gq, gk, gv, ge, gws, gwo, ctx.alpha)
         return gq, gk, gv, ge, gws, gwo, None
 
 
@@ -156,6 +211,7 @@ class _AttnBlock(Function):
         # ppre .. pbeta: LNHandle of the LayerNorm that produced y (or None): its backward can then run in the
         # epilogue of this node's dy GEMM, the result leaving as the gradient of `ppre` instead of `y`
         B, N, C = x1.shape
+        _check_neighbours(N)
         x1f, yf = _c(x1).reshape(-1, C), _c(y).reshape(-1, C)
         adt = x1f.dtype
         pw = lambda w_, m_: packed_weight(w_, m_, adt)
@@ -192,10 +248,7 @@ class _AttnBlock(Function):
         else:
             e = row_gemm(yf, pw(we, 0), C, C, bias=be)
             s = torch.empty_like(e) if need_edge else None
-            with _dev(q):
-                _lib.check(lib.dg_attn_core_fwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(e), _lib.ptr(s),
-                                                _lib.ptr(o), B, N, C, alpha, _lib.dt(q), _lib.stream_of(q)), "dg_attn_core_fwd")
-            _account("attn_fwd", q.element_size() * B * ((2 if need_edge else 1) * N * N * C + 4 * N * C))
+            _core_fwd(q, k, v, e, s, o, alpha, B, N, C)
         r3 = row_gemm(o, pw(won, 0), C, C, bias=bon, residual=x1f, ln=(_c(g3), _c(b3), eps3), want_pre=keep)
         x2, mean3, rstd3, pre3 = r3 if keep else (*r3, None)
         outs = [x2.view(B, N, C)]
@@ -275,31 +328,17 @@ class _AttnBlock(Function):
 
 
 def _attn_bwd_launch(q, k, v, e, ws, wo, alpha, add_e=None):
-    B, N, C = q.shape[0], q.shape[1], q.shape[2]
-    lib = _lib.load()
     dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
     de = torch.empty_like(e)
-    with _dev(q):
-        _lib.check(lib.dg_attn_core_bwd_add(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(e), _lib.ptr(ws),
-                                            _lib.ptr(wo), _lib.ptr(add_e), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv),
-                                            _lib.ptr(de), B, N, C, alpha, _lib.dt(q), _lib.stream_of(q)),
-                   "dg_attn_core_bwd")
-    _account("attn_bwd", q.element_size() * B * ((2 + (ws is not None) + (add_e is not None)) * N * N * C + 7 * N * C))
+    _core_bwd(q, k, v, e, ws, wo, add_e, dq, dk, dv, de, alpha)
     return dq, dk, dv, de
 
 
 def _attn_bwd2_launch(q, k, v, e, ws, wo, tq, tk, tv, te, alpha):
-    B, N, C = q.shape[0], q.shape[1], q.shape[2]
-    lib = _lib.load()
     gq, gk, gv, gwo = (torch.empty_like(q) for _ in range(4))
     ge = torch.empty_like(e)
     gws = torch.empty_like(e) if ws is not None else None
-    with _dev(q):
-        _lib.check(lib.dg_attn_core_bwd2(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(e), _lib.ptr(ws), _lib.ptr(wo),
-                                         _lib.ptr(tq), _lib.ptr(tk), _lib.ptr(tv), _lib.ptr(te), _lib.ptr(gq),
-                                         _lib.ptr(gk), _lib.ptr(gv), _lib.ptr(ge), _lib.ptr(gws), _lib.ptr(gwo),
-                                         B, N, C, alpha, _lib.dt(q), _lib.stream_of(q)), "dg_attn_core_bwd2")
-    _account("attn_bwd2", q.element_size() * B * ((5 if ws is not None else 3) * N * N * C + 11 * N * C))
+    _core_bwd2(q, k, v, e, ws, wo, tq, tk, tv, te, gq, gk, gv, ge, gws, gwo, alpha)
     return gq, gk, gv, ge, gws, gwo
 
 

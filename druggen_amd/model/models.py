@@ -70,6 +70,7 @@ class _Trunk(nn.Module):
         if not parts[0].is_cuda:
             raise RuntimeError("druggen_amd modules run on MI355X only (no CPU fallback): move the model and "
                                "its inputs to a GPU device")
+        dgf._check_neighbours(parts[0].shape[1])      # the attention core's limit, before the first launch
         adt = dgf.activation_dtype()      # storage of the encoder activations (float32, or bfloat16: configs[2])
         node = self._embed(self.node_layers, z_n)
         if node.dtype != adt:

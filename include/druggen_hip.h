@@ -27,7 +27,7 @@
  *    replicas (reference train.py:220-223).
  *
  * Shapes: B molecules, N = vertexes, C = dim (C % 4 == 0, C >= 8, N <= 96 for
- * the attention kernels), R = number of rows of a [R, C] row matrix.
+ * the attention kernels, N <= 256 for dg_attn_core_long_*), R = number of rows of a [R, C] row matrix.
  */
 #ifndef DRUGGEN_HIP_H
 #define DRUGGEN_HIP_H
@@ -120,6 +120,29 @@ int dg_attn_core_bwd2(const void* q, const void* k, const void* v, const void* e
                       const void* tq, const void* tk, const void* tv, const void* te,
                       void* gq, void* gk, void* gv, void* ge, void* gws, void* gwo,
                       int B, int N, int C, float alpha, int dtype, dg_stream_t stream);
+
+/* ---- graph attention core for long neighbour lists (1 <= N <= 256): src/model/layers.py:119-134 ----
+ * Added after DG_VERSION 232 without a version bump: the entries above are unchanged and still stop at N = 96.
+ * Same math, operands and NULL rules as dg_attn_core_fwd / dg_attn_core_bwd_add / dg_attn_core_bwd2:
+ *   s[b,i,j,c] = alpha * q[b,i,c] * k[b,j,c] * (e^2 + e)[b,i,j,c];  p = softmax_j(s);  o[b,i,c] = sum_j p v[b,j,c]
+ * q,k,v,o and every [B,N,C] gradient: [B,N,C];  e,s,ws,add_e,de,te,ge,gws: [B,N,N,C].
+ * Shapes: 1 <= N <= 256, C % 4 == 0, C >= 8 (others DG_E_SHAPE).  A row of e is read once; the column sums (dk, dv,
+ * gk, gv) are combined in a fixed order through `workspace` (float32 partials of the row groups), so results are
+ * bit-reproducible; workspace_bytes >= dg_attn_core_long_workspace_bytes(B, N, C) (0 for N <= 32: workspace may then
+ * be NULL), else DG_E_WORKSPACE.  Profiler keys: DG_K_ATTN_FWD / _BWD / _BWD2.                                    */
+size_t dg_attn_core_long_workspace_bytes(int B, int N, int C);
+/* forward; s may be NULL */
+int dg_attn_core_long_fwd(const void* q, const void* k, const void* v, const void* e, void* s, void* o,
+                          int B, int N, int C, float alpha, int dtype, dg_stream_t stream);
+/* first-order backward; ws (NULL = zeros) and add_e (NULL, or added to de on its way out) may be NULL */
+int dg_attn_core_long_bwd(const void* q, const void* k, const void* v, const void* e, const void* ws, const void* wo,
+                          const void* add_e, void* dq, void* dk, void* dv, void* de, void* workspace,
+                          size_t workspace_bytes, int B, int N, int C, float alpha, int dtype, dg_stream_t stream);
+/* second order (tests/kernel_math.py::attn_core_bwd2); ws and gws may be NULL */
+int dg_attn_core_long_bwd2(const void* q, const void* k, const void* v, const void* e, const void* ws, const void* wo,
+                           const void* tq, const void* tk, const void* tv, const void* te,
+                           void* gq, void* gk, void* gv, void* ge, void* gws, void* gwo, void* workspace,
+                           size_t workspace_bytes, int B, int N, int C, float alpha, int dtype, dg_stream_t stream);
 
 /* ---- fused attention half of the edge branch: src/model/layers.py:116-135 + 186-190 ----
  *   e  = y We^T + be                       (layers.py:116; never written to HBM)
