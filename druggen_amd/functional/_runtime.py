@@ -102,20 +102,33 @@ def set_hidden_storage(mode: str) -> None:
     options.hidden = mode
 
 
-def hidden_forward_storage() -> str:
+# Above this many atoms the default mode keeps the backward's hidden tensors in 24 bits (the "dh24" pairing) instead of the fp16
+# plane: a node's gradient sums N edge rows' fp16 roundings while their signal cancels (softmax), so the spend grows with N --
+# worst golden tensor 6.4e-4 at N = 128 with dh16 (tests/test_hip_model.py::test_parity_margin_tripwire allows 6e-4), 3.8e-5
+# with dh24.
+DH16_MAX_ATOMS = 96
+
+
+def _long_rows(x) -> bool:
+    """``x`` ([B,N,C] node or [B,N,N,C] edge rows) belongs to molecules of more than DH16_MAX_ATOMS atoms."""
+    return x.dim() >= 3 and x.shape[-2] > DH16_MAX_ATOMS
+
+
+def hidden_forward_storage(long_rows: bool = False) -> str:
     """Storage of the FORWARD's h = relu(fc1 x) when it goes through HBM in the default mode: "split" -- the float32-class
     hi / lo fp16 split under one row scale, done once by the launch that writes h (DG_DTYPE_F32_H32: fc2's launch only moves the
-    planes, the weight gradient dW2 = dz^T h reads the hi plane alone) -- or "f32" (every other mode)."""
-    return "split" if hidden_storage() == "dh16" else "f32"
+    planes, the weight gradient dW2 = dz^T h reads the hi plane alone) -- or "f32" (every other mode, and molecules of more than
+    DH16_MAX_ATOMS atoms, whose backward then stores dh in 24 bits: ``_ffn_bwd_codes``)."""
+    return "split" if hidden_storage() == "dh16" and not long_rows else "f32"
 
 
-def _hidden_code(adt) -> int:
+def _hidden_code(adt, long_rows: bool = False) -> int:
     """ABI dtype code of the FORWARD's hidden tensor h for activations of ``adt``."""
     if adt == torch.float32:
         mode = hidden_storage()
         if mode in ("f16", "f24"):
             return _lib.F32_H16 if mode == "f16" else _lib.F32_H24
-        if hidden_forward_storage() == "split":
+        if hidden_forward_storage(long_rows) == "split":
             return _lib.F32_H32
     return _lib.DTYPES[adt]
 
@@ -140,6 +153,9 @@ def _ffn_bwd_codes(h, adt, R: int, H: int):
             return _lib.F32_H32_DH16, _lib.F32_H16
         return code, code
     dh_code = _hidden_code_bwd(adt)
+    if dh_code == _lib.F32_H16 and hidden_storage() == "dh16":
+        # float32 h in the default mode: the forward took molecules of more than DH16_MAX_ATOMS atoms -- dh in 24 bits
+        dh_code = _lib.F32_H24
     if dh_code == _lib.F32_H16:
         return _lib.F32_DH16, dh_code
     if dh_code == _lib.F32_H24:

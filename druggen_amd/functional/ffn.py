@@ -61,12 +61,12 @@ def set_fused_ffn_f32(on: bool) -> None:
     options.ffn_f32 = "fused" if on else "unfused"
 
 
-def fused_ffn_f32_supported(x2, w1, w2) -> bool:
+def fused_ffn_f32_supported(x2, w1, w2, long_rows: bool = False) -> bool:
     """dg_ffn_ln_fwd_f32 serves float32 rows, dim 128, hidden 384, in the default hidden-storage mode: what it leaves for the
     backward is the hi fp16 plane of h (a DG_DTYPE_F32_H16 buffer) -- exactly what the default mode's backward reads of the
     pre-split h (dW2 = dz^T h_hi)."""
     return (options.ffn_f32 == "fused" and x2.is_cuda and x2.dtype == torch.float32 and tuple(w1.shape) == (384, 128)
-            and tuple(w2.shape) == (128, 384) and hidden_storage() == "dh16")
+            and tuple(w2.shape) == (128, 384) and hidden_storage() == "dh16" and not long_rows)
 
 
 def _ffn_f32_fwd_args(p, keep):
@@ -98,11 +98,12 @@ class _FFNLN(Function):
         R = x2.shape[0]
         lib = _lib.load()
         dev = x2.device
-        adt, code, es = x2.dtype, _hidden_code(x2.dtype), x2.element_size()
+        long_rows = _long_rows(x)
+        adt, code, es = x2.dtype, _hidden_code(x2.dtype, long_rows), x2.element_size()
         # no input needs a gradient (e.g. the Generator's forward inside the D step): nothing is kept for a backward --
         # no pre-LayerNorm sum (one [R,C] write pass) and no ReLU bit mask
         keep = any(ctx.needs_input_grad)
-        fused = fused_ffn_f32_supported(x2, w1, w2)
+        fused = fused_ffn_f32_supported(x2, w1, w2, long_rows)
         if fused:      # h stays on chip; its hi fp16 plane leaves for the backward's dW2 (a DG_DTYPE_F32_H16 buffer)
             code = _lib.F32_H16
         y = torch.empty(R, C, dtype=adt, device=dev)
@@ -267,13 +268,14 @@ class _FFNLNPair(Function):
             x2 = _c(inp).reshape(-1, C)
             R = x2.shape[0]
             dev, adt = x2.device, x2.dtype
-            code = _hidden_code(adt)
-            fused = fused_ffn_f32_supported(x2, w1, w2) and (not probs or probs[0]["fused"])
+            long_rows = _long_rows(inp)
+            code = _hidden_code(adt, long_rows)
+            fused = fused_ffn_f32_supported(x2, w1, w2, long_rows) and (not probs or probs[0]["fused"])
             if fused:      # (both problems or neither: one launch carries them)
                 code = _lib.F32_H16
             elif probs and probs[0]["fused"]:
                 probs[0]["fused"] = False
-                probs[0]["code"] = _hidden_code(adt)
+                probs[0]["code"] = _hidden_code(adt, long_rows)
                 probs[0]["h"] = _hidden_empty(probs[0]["R"], probs[0]["H"], adt, probs[0]["code"], dev)
             probs.append(dict(
                 inp=inp, x2=x2, R=R, C=C, H=H, code=code, w1=w1, b1=b1, w2=w2, b2=b2, gamma=gamma, beta=beta, fused=fused,

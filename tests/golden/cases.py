@@ -42,6 +42,11 @@ CASES = {
     # BASELINE.json configs[4] geometry (N=90 atoms, 10 bond types) at depth 2, batch 2
     "c5_b2": dict(cfg=dict(act="relu", vertexes=90, edges=10, nodes=13, dim=128, depth=2, heads=8, mlp_ratio=3),
                   batch=2, submodel="NoTarget", seed=25, lambda_gp=10.0, full=False),
+    # Long molecules (97-256 atoms): the attention core's long-neighbour-list path
+    "long128_b2": dict(cfg=dict(act="relu", vertexes=128, edges=5, nodes=13, dim=128, depth=2, heads=8, mlp_ratio=3),
+                       batch=2, submodel="DrugGEN", seed=26, lambda_gp=10.0, full=False),
+    "long256_b1": dict(cfg=dict(act="leaky", vertexes=256, edges=5, nodes=13, dim=128, depth=1, heads=8, mlp_ratio=3),
+                       batch=1, submodel="NoTarget", seed=27, lambda_gp=10.0, full=False),
     # Real molecular graphs: SMILES shipped with the reference's results (tests/golden/chembl_like_smiles.csv),
     # featurised by druggen_amd.smiles with the atom / bond tables the reference's encoder construction
     # (src/data/utils.py:70-126) yields over those result files: atoms {PAD,B,C,N,O,F,P,S,Cl}, bonds
@@ -119,3 +124,38 @@ def summarise(arr: np.ndarray, index: int) -> np.ndarray:
 
 def fixture_path(name: str) -> str:
     return os.path.join(HERE, name + ".npz")
+
+
+# Outputs kept whole in every fixture whose element count passes PACK_MIN_ELEMENTS (the generator's edge sample from N = 128 on)
+# are stored in half the bytes: "ref32/<key>" as float32 (the float32 run's own values: exact) and "ref64/<key>" as its offset
+# from them, quantised to int16 under one float64 scale ("<key>.q16", "<key>.scale").  The offset is ~1e-6 of the values, so the
+# unpacked float64 tensor is within ~2e-11 of the reference's (norm-wise relative; ``pack_outputs`` asserts 1e-10), far inside
+# the tightest comparison made with it (the float64 oracle at 1e-9).
+PACK_MIN_ELEMENTS = 1 << 17
+PACKED_OUTPUTS = ("G.edge_sample",)
+
+
+def pack_outputs(store: dict) -> None:
+    for key in PACKED_OUTPUTS:
+        e64, e32 = store[f"ref64/{key}"], store[f"ref32/{key}"]
+        if e64.size < PACK_MIN_ELEMENTS:
+            continue
+        low = e32.astype(np.float32)
+        assert np.array_equal(low.astype(np.float64), e32), key
+        d = e64 - e32
+        scale = float(np.abs(d).max()) / 32767.0 or 1.0
+        q = np.round(d / scale).astype(np.int16)
+        back = e32 + q.astype(np.float64) * scale
+        assert np.linalg.norm(back - e64) <= 1e-10 * np.linalg.norm(e64), key
+        store[f"ref32/{key}"] = low
+        store[f"ref64/{key}.q16"], store[f"ref64/{key}.scale"] = q, np.float64(scale)
+        del store[f"ref64/{key}"]
+
+
+def unpack_outputs(fx: dict) -> dict:
+    for key in PACKED_OUTPUTS:
+        if f"ref64/{key}.q16" in fx:
+            e32 = fx[f"ref32/{key}"].astype(np.float64)
+            fx[f"ref32/{key}"] = e32
+            fx[f"ref64/{key}"] = e32 + fx.pop(f"ref64/{key}.q16").astype(np.float64) * float(fx.pop(f"ref64/{key}.scale"))
+    return fx

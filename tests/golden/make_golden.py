@@ -139,6 +139,7 @@ def main(names=None):
             for k in list(store):       # big activations -> summaries
                 if k.endswith(("G.node", "G.edge")):
                     store[k] = cases.summarise(store[k], 999)
+        cases.pack_outputs(store)
         np.savez_compressed(cases.fixture_path(name), **store)
         print(f"{name}: {os.path.getsize(cases.fixture_path(name)) / 1024:.0f} KiB  "
               f"d_loss={float(store['ref64/d_loss']):.6f} g_loss={float(store['ref64/g_loss']):.6f} "

@@ -19,7 +19,7 @@ import cases  # noqa: E402
 
 def load_fixture(name):
     z = np.load(cases.fixture_path(name), allow_pickle=False)
-    return {k: z[k] for k in z.files}
+    return cases.unpack_outputs({k: z[k] for k in z.files})
 
 
 def run_step(G, D, d_loss_fn, g_loss_fn, inputs, lambda_gp, lr=1e-5):

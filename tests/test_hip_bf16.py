@@ -374,20 +374,18 @@ def test_embed_sym_bwd_bf16_rejects_unsupported_arguments():
     assert lib.dg_embed_sym_bwd_bf16_workspace_bytes(0, 9) == 0
 
 
-def test_bf16_step_against_the_fp32_hip_path_at_batch_32():
-    """The bf16 configuration at a batch where gradients are averages over molecules (configs[1] model, B = 32, default
-    init, synthetic graphs): every parameter gradient of the D step and of the G step against the fp32 HIP path on the
-    same weights / batch / eps, with the error model of the fp32 tests (per tensor ||got - want|| / max(||want||,
-    ||all|| / sqrt(n))): worst tensor <= 10 %, median <= 0.5 %, all gradients as one vector <= 8 %, losses <= 2e-3."""
+def _bf16_step_against_fp32(B, N, E, M, depth):
+    """Every parameter gradient of the D step and of the G step, and both losses, of the bf16 configuration against the
+    fp32 HIP path on the same default-init weights, synthetic batch and eps, with the error model of the fp32 tests (per
+    tensor ||got - want|| / max(||want||, ||all|| / sqrt(n))) and the BF16_B32_* bounds."""
     from druggen_amd import functional as dgf, synth
     from druggen_amd.model import Discriminator, Generator, discriminator_loss, generator_loss
-    B, N, E, M = 32, 45, 5, 13
     dev = torch.device("cuda")
 
     def run(mode):
         torch.manual_seed(0)
         ctor = ("relu", N, E, M, 0.0)
-        kw = dict(dim=128, depth=4, heads=8, mlp_ratio=3)
+        kw = dict(dim=128, depth=depth, heads=8, mlp_ratio=3)
         G, D = Generator(*ctor, **kw).to(dev), Discriminator(*ctor, **kw).to(dev)
         a, x, _, _ = synth.molecule_batch(B, N, E, M, seed=1234)
         da, dx, _, _ = synth.molecule_batch(B, N, E, M, seed=2234)
@@ -423,3 +421,15 @@ def test_bf16_step_against_the_fp32_hip_path_at_batch_32():
         print(f"{net}: worst {errs[0][0]:.4f} ({errs[0][1]}) median {med:.5f} global {glob:.4f}")
         assert errs[0][0] <= BF16_B32_GRAD_WORST, errs[:3]
         assert med <= BF16_B32_GRAD_MEDIAN and glob <= BF16_B32_GRAD_GLOBAL, (med, glob)
+
+
+def test_bf16_step_against_the_fp32_hip_path_at_batch_32():
+    """The bf16 configuration at a batch where gradients are averages over molecules (configs[1] model, B = 32, default
+    init, synthetic graphs): worst tensor <= 10 %, median <= 0.5 %, all gradients as one vector <= 8 %, losses <= 2e-3."""
+    _bf16_step_against_fp32(B=32, N=45, E=5, M=13, depth=4)
+
+
+def test_bf16_step_against_the_fp32_hip_path_at_128_atoms():
+    """As above with molecules of 128 atoms (two blocks): the attention runs the long core (csrc/attn_core_long.hip) and
+    the edge tensors are eight times longer per molecule; same bounds."""
+    _bf16_step_against_fp32(B=32, N=128, E=5, M=13, depth=2)

@@ -86,6 +86,72 @@ def test_long_attn_core_forward_backward_second_order(B, N, C):
         assert _rel(got, want) < 5 * TOL, name
 
 
+# The geometry switches of DESIGN 3.18 (forward slots per thread 4 / 6 / 8 above N = 96 / 128 / 192; backward 8-quad slices up
+# to N = 128; second order 4-quad slices up to N = 192; C < 20 on 4-quad slices; G = ceil(N / 32) row groups, no workspace for
+# N <= 32), the short shapes through the long entries, and batches past the first group of 8 molecules (place() pads the
+# grid to a multiple of 8 and gives molecule b the XCD residue b % 8; the reverse walk mirrors over the padded count).
+BOUNDARY_SHAPES = [(1, 1, 128), (1, 32, 128), (1, 33, 128), (1, 96, 128), (1, 129, 128), (1, 192, 128), (1, 193, 128),
+                   (1, 255, 128), (1, 256, 16), (1, 161, 48), (9, 97, 32), (17, 97, 32), (9, 193, 32), (17, 193, 32)]
+SENTINEL = -1.5e38
+
+
+def _guarded(B, shape):
+    """[Bpad, *shape] float32 buffer filled with SENTINEL, Bpad = B rounded up to a multiple of 8 (the molecules place()
+    pads the grid with): the launch gets its first B molecules, the rest is the guard region."""
+    return torch.full(((B + 7) // 8 * 8,) + tuple(shape), SENTINEL, dtype=torch.float32, device="cuda")
+
+
+def _closed_forms_per_molecule(ops, t, alpha, b):
+    q, k, v, e, ws, wo = (x[b:b + 1] for x in ops)
+    s, o = km.attn_core_fwd(q, k, v, e, alpha)
+    g = km.attn_core_bwd(q, k, v, e, ws, wo, alpha)
+    h = km.attn_core_bwd2(q, k, v, e, ws, wo, *(x[b:b + 1] for x in t), alpha)
+    return dict(zip("s o dq dk dv de gq gk gv ge gws gwo".split(), (s, o) + tuple(g) + tuple(h)))
+
+
+@gpu
+@pytest.mark.parametrize("B,N,C", BOUNDARY_SHAPES)
+def test_long_attn_core_at_its_geometry_switches_per_molecule(B, N, C):
+    """dg_attn_core_long_fwd / _bwd / _bwd2 called directly (N <= 96 included) against the fp64 closed forms, molecule by
+    molecule, so that a dropped, duplicated or misplaced molecule fails by name.  Outputs live in buffers padded to a
+    multiple of 8 molecules and pre-filled with a sentinel: every molecule < B must be written, none past B.  The three
+    launches run twice: when B N^2 reaches DG_EDGE_ROWS, consecutive launches alternate direction (csrc/traversal.h), so
+    every kernel walks the molecules both ways."""
+    from druggen_amd import _lib
+    alpha = 1.0 / math.sqrt(max(C // 4, 1))
+    ops64 = _operands(B, N, C)
+    t64 = ops64[6]
+    q, k, v, e, ws, wo = (x.float().cuda() for x in ops64[:6])
+    tq, tk, tv, te = (x.float().cuda() for x in t64)
+    lib = _lib.load()
+    assert (lib.dg_attn_core_long_workspace_bytes(B, N, C) == 0) == (N <= 32)
+    row, edge = (N, C), (N, N, C)
+    runs = []
+    for _ in range(2):
+        out = dict(s=_guarded(B, edge), o=_guarded(B, row))
+        out.update(dq=_guarded(B, row), dk=_guarded(B, row), dv=_guarded(B, row), de=_guarded(B, edge))
+        out.update(gq=_guarded(B, row), gk=_guarded(B, row), gv=_guarded(B, row), ge=_guarded(B, edge),
+                   gws=_guarded(B, edge), gwo=_guarded(B, row))
+        _long_launch("fwd", q, k, v, e, out["s"], out["o"], B=B, N=N, C=C, alpha=alpha)
+        _long_launch("bwd", q, k, v, e, ws, wo, None, *(out[n] for n in "dq dk dv de".split()), B=B, N=N, C=C, alpha=alpha)
+        _long_launch("bwd2", q, k, v, e, ws, wo, tq, tk, tv, te, *(out[n] for n in "gq gk gv ge gws gwo".split()),
+                     B=B, N=N, C=C, alpha=alpha)
+        torch.cuda.synchronize()
+        runs.append({n: x.cpu() for n, x in out.items()})
+        del out
+    for name in runs[0]:
+        for r, run in enumerate(runs):
+            guard = run[name][B:]
+            assert bool((guard == SENTINEL).all()), f"{name}: written past molecule {B - 1} (run {r})"
+    for b in range(B):
+        want = _closed_forms_per_molecule(ops64[:6], t64, alpha, b)
+        for name, ref in want.items():
+            tol = TOL if name in ("s", "o", "dq", "dk", "dv", "de") else 5 * TOL
+            for r, run in enumerate(runs):
+                err = _rel(run[name][b:b + 1], ref)
+                assert err < tol, f"molecule {b}: {name} rel err {err:.3g} (run {r})"
+
+
 @gpu
 def test_long_attn_core_without_score_output_and_null_ws():
     from druggen_amd import functional as dgf
@@ -109,9 +175,9 @@ def test_long_attn_core_without_score_output_and_null_ws():
 
 @gpu
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-def test_long_attn_core_backward_adds_an_outside_adjoint_of_e(dtype):
+@pytest.mark.parametrize("B,N,C", [(2, 128, 128), (1, 129, 128), (1, 193, 128)])   # 8-quad, 4-quad (N > 128) backward slices
+def test_long_attn_core_backward_adds_an_outside_adjoint_of_e(B, N, C, dtype):
     from druggen_amd import functional as dgf
-    B, N, C = 2, 128, 128
     f = lambda shape, s, sc=1.0: (_gen(shape, s) * sc).to(dtype).cuda()
     q, k, v, wo = f((B, N, C), 1), f((B, N, C), 2), f((B, N, C), 3), f((B, N, C), 6)
     e, ws, ae = f((B, N, N, C), 4, 0.8), f((B, N, N, C), 5), f((B, N, N, C), 11, 0.5)
@@ -158,11 +224,13 @@ def test_long_entries_match_the_short_ones_where_both_run(B, N, C):
 
 # ---------------------------------------------------------------------------------------- reproducibility
 @gpu
-def test_long_attn_core_is_bit_reproducible_in_both_directions():
-    """B N^2 = 65536 rows: every launch is edge-level, so consecutive launches walk the molecules in opposite directions
-    (csrc/traversal.h); three launches per repetition put each kernel on both directions across the repetitions."""
+@pytest.mark.parametrize("B,N,C", [(4, 128, 128), (9, 193, 32)])
+def test_long_attn_core_is_bit_reproducible_in_both_directions(B, N, C):
+    """B N^2 >= 65536 rows: every launch is edge-level, so consecutive launches walk the molecules in opposite directions
+    (csrc/traversal.h); three launches per repetition put each kernel on both directions across the repetitions.  B = 9:
+    the reverse walk mirrors over the padded count of 16 molecules."""
     from druggen_amd import functional as dgf
-    B, N, C, alpha = 4, 128, 128, 0.25
+    alpha = 0.25
     f = lambda shape, s: _gen(shape, s).float().cuda().requires_grad_(True)
     q, k, v, e = f((B, N, C), 1), f((B, N, C), 2), f((B, N, C), 3), f((B, N, N, C), 4)
     ws, wo = f((B, N, N, C), 5), f((B, N, C), 6)
@@ -181,9 +249,10 @@ def test_long_attn_core_is_bit_reproducible_in_both_directions():
 
 # ---------------------------------------------------------------------------------------- bf16 vs fp32
 @gpu
-def test_long_attn_core_bf16_against_float32():
+@pytest.mark.parametrize("B,N,C", [(2, 128, 128), (9, 193, 32), (9, 256, 32)])
+def test_long_attn_core_bf16_against_float32(B, N, C):
     from druggen_amd import functional as dgf
-    B, N, C, alpha = 2, 128, 128, 0.25
+    alpha = 0.25
     base = [x.to(torch.bfloat16) for x in _operands(B, N, C)[:6]]
     tb = [x.to(torch.bfloat16) for x in _operands(B, N, C)[6]]
     res = {}
@@ -198,6 +267,12 @@ def test_long_attn_core_bf16_against_float32():
         assert a.dtype == torch.bfloat16 and _rel(a, b) < TOL_IO
     for a, b in zip(res[torch.bfloat16][1], res[torch.float32][1]):
         assert _rel(a, b) < 2 * TOL_IO
+    for m in range(B):      # molecule by molecule
+        for tol, got, want in ((TOL_IO, res[torch.bfloat16][0], res[torch.float32][0]),
+                               (2 * TOL_IO, res[torch.bfloat16][1], res[torch.float32][1])):
+            for i, (a, b) in enumerate(zip(got, want)):
+                err = _rel(a[m], b[m])
+                assert err < tol, f"molecule {m}: output {i} rel err {err:.3g}"
 
 
 # ----------------------------------------------------------------------------------------------- limits
@@ -239,6 +314,9 @@ def test_long_entries_validate_arguments_without_a_gpu():
     assert lib.dg_attn_core_long_fwd(*[fake] * 6, 1, 128, 6, 0.25, 0, None) == -1     # C % 4 != 0
     need = lib.dg_attn_core_long_workspace_bytes(2, 128, 128)
     assert need > 0 and lib.dg_attn_core_long_workspace_bytes(2, 32, 128) == 0
+    for B, C in ((1, 8), (9, 48), (17, 128)):    # one row group (no column partials) exactly up to 32 neighbours
+        for N in range(1, 257):
+            assert (lib.dg_attn_core_long_workspace_bytes(B, N, C) == 0) == (N <= 32), (B, N, C)
     assert lib.dg_attn_core_long_bwd(*[fake] * 12, need - 1, 2, 128, 128, 0.25, 0, None) == -3
     assert b"workspace too small" in lib.dg_last_error_string()
     assert lib.dg_attn_core_long_bwd2(*[fake] * 16, None, need, 2, 128, 128, 0.25, 0, None) == -3

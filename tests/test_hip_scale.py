@@ -31,7 +31,8 @@ def _batch(B, N, E, seed):
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
-@pytest.mark.parametrize("name,B,N,E,L", [("configs[3] B=2048", 2048, 45, 5, 4), ("configs[4] N=90 L=8", 64, 90, 10, 8)])
+@pytest.mark.parametrize("name,B,N,E,L", [("configs[3] B=2048", 2048, 45, 5, 4), ("configs[4] N=90 L=8", 64, 90, 10, 8),
+                                          ("N=128 L=2", 16, 128, 5, 2)])
 def test_full_size_shard_consistency_and_permutation_equivariance(name, B, N, E, L, dtype):
     """(i) per-molecule outputs do not depend on the rest of the batch: the logits of the full batch equal the
     concatenation of two half-batch shards and the mean-loss gradient the average of the shard gradients (the
