@@ -20,11 +20,18 @@ Rank 0 prints ONE JSON line of < 6 KB.  Besides the contract fields it carries
                 steps, against the 8 TB/s HBM3E peak (+ its MFMA-side fraction, its
                 kernel symbol, and the same rate against the section-8d FLOOR bytes:
                 inputs + outputs only, nothing saved for a backward);
-  roofline_attention  the same for the attention kernel north_star names;
+  roofline_attention  the same for the attention kernel north_star names.
+A plain run does only that: set up, warm up, the instrumented step, the timed steps, the dump, the line.
+`--full` adds everything measured beside the headline, after the timed steps:
+  step_hbm, kernels, roofline_all  two more fully instrumented steps; the per-kernel table
+                (`kernels`, `roofline_all`) goes to profiles/bench_detail_<config>_<dtype>.json, not to stdout;
+  hip_graph_replay_same_step, strict_f32_hidden  the same steps replayed from a captured hipGraph, and
+                with the feed-forward's hidden tensors in plain float32;
+  bf16_configs2 BASELINE configs[2] (bf16 activations, batch 2048) in the same process;
   cpu_baseline  the oracle (CPU restatement of the reference path) timed on the
-                host cores on a bounded sample of the same workload.
-The per-kernel table of every profiled HIP kernel (`kernels`, `roofline_all`) goes to
-profiles/bench_detail_<config>_<dtype>.json (and gpurun_out/ when that exists), not to stdout.
+                host cores on a bounded sample of the same workload;
+  parity_margin the committed golden-parity margin of the hidden-storage mode;
+  replicas_identical  N > 1: per-tensor checksums of G and D compared across ranks (also with --check-replicas).
 `--dump-outputs DIR` writes what the last timed step returned (both losses, the updated G and D
 parameters) as DIR/<name>.npy, so that two builds can be compared output for output.
 """
@@ -66,19 +73,23 @@ def parse():
     ap.add_argument("--batch", type=int, default=0, help="molecules per GPU (0 = the configuration's)")
     ap.add_argument("--dtype", choices=["f32", "bf16"], default=None,
                     help="storage of the encoder activations (default: the configuration's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what lies beside the headline: the per-kernel table, "
+                         "the hipGraph-replay and strict-float32 regions, the bf16 configs[2] line, the CPU baseline, the "
+                         "parity margin and (N > 1) the cross-rank replica comparison")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--check-replicas", action="store_true",
-                    help="N > 1: exit non-zero when the per-tensor checksums of G and D differ across ranks after the timed "
-                         "steps (the comparison itself always runs for N > 1 and is reported as replicas_identical)")
+                    help="N > 1: compare the per-tensor checksums of G and D across ranks after the timed steps (as --full "
+                         "does, reported as replicas_identical) and exit non-zero when they differ")
     ap.add_argument("--graph", action="store_true", help="time hipGraph replays only and skip the eagerly launched, event-instrumented "
                     "region (one graph per step on one GPU; N > 1: three graphs per step, cut at the two gradient all-reduces)")
     ap.add_argument("--eager", action="store_true",
-                    help="time the eagerly launched steps only (skip the secondary hipGraph-replay and strict-float32 regions)")
+                    help="--full: skip the secondary hipGraph-replay and strict-float32 regions")
     ap.add_argument("--vertexes", type=int, default=0, help="override N (parity-case shapes; not the headline)")
     ap.add_argument("--depth", type=int, default=0, help="override L")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the secondary measurement (BASELINE configs[2]: bf16 activations, batch 2048) that the "
-                         "default single-GPU run appends as `bf16_configs2` after the timed region")
+                    help="--full: skip the secondary measurement (BASELINE configs[2]: bf16 activations, batch 2048) that "
+                         "a single-GPU run appends as `bf16_configs2` after the timed region")
     ap.add_argument("--cpu-batch", type=int, default=32)
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = the reference's own setting (train.py:16: 5 threads)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -338,21 +349,23 @@ def main():
     stepper.time_collectives(False)
     attn_stats = {k: (_lib.prof_read(k), dgf.traffic_bytes(k), dgf.traffic_floor_bytes(k)) for k in attn_kernels}
     traffic_flops = {k: dgf.traffic_flops(k) for k in attn_kernels}
+    # ---- everything below up to the result line, bar the N > 1 timing, runs with --full only
     # per-kernel table of every HIP kernel: two extra, untimed, fully instrumented steps
-    _lib.prof_reset()
-    dgf.traffic_reset()
-    _lib.prof_enable(True)
-    detail_steps = 2
-    t1 = time.perf_counter()
-    for _ in range(detail_steps):
-        stepper.step(disc_edge, disc_node, gen_edge, gen_node)
-    sync()
-    detail_elapsed = time.perf_counter() - t1
-    _lib.prof_enable(False)
-    # (functional._account keeps counting bytes whenever a step is traced in Python: read the two instrumented steps' totals
-    # before the graph region below warms up and captures)
-    detail_traffic = {name: (dgf.traffic_bytes(name), dgf.traffic_floor_bytes(name), dgf.traffic_flops(name))
-                      for name in _lib.KERNEL_IDS}
+    detail_steps, detail_elapsed, detail_traffic = 2, None, {}
+    if args.full:
+        _lib.prof_reset()
+        dgf.traffic_reset()
+        _lib.prof_enable(True)
+        t1 = time.perf_counter()
+        for _ in range(detail_steps):
+            stepper.step(disc_edge, disc_node, gen_edge, gen_node)
+        sync()
+        detail_elapsed = time.perf_counter() - t1
+        _lib.prof_enable(False)
+        # (functional._account keeps counting bytes whenever a step is traced in Python: read the two instrumented steps'
+        # totals before the graph region below warms up and captures)
+        detail_traffic = {name: (dgf.traffic_bytes(name), dgf.traffic_floor_bytes(name), dgf.traffic_flops(name))
+                          for name in _lib.KERNEL_IDS}
     # ---- secondary regions at the headline, reported BESIDE `value` (which is always the eagerly launched region above):
     # (1) the same K steps replayed from a captured hipGraph (trainer.GraphedGANStep; N > 1: three graphs per step cut at the two
     # gradient all-reduces).  A step is ~700 launches issued from Python, 30-40 ms of host work against ~50 ms of GPU work at
@@ -363,7 +376,7 @@ def main():
     # (2) `strict_f32_hidden`: the same steps with the feed-forward's [R,384] hidden tensors in plain float32 (hidden storage
     # "f32": no fp16 plane for dh, no fused forward) -- the number the default mode's precision trade is measured against.
     graph_region = None
-    want_graph = (not args.graph and not args.eager and args.config == "c2" and act_dtype == "f32"
+    want_graph = (args.full and not args.graph and not args.eager and args.config == "c2" and act_dtype == "f32"
                   and not stepper._low_memory(gen_edge))
     if want_graph:
         graphed, err = None, None
@@ -427,7 +440,7 @@ def main():
     allreduce = None
     if world > 1:
         # what an N-GPU line needs to explain itself: the time between the events around the two all-reduces of a step
-        # on every rank (includes waiting for the slowest rank), and whether the replicas still hold identical weights
+        # on every rank (includes waiting for the slowest rank)
         mine = torch.tensor([ms_ar / max(1, args.steps)], device=dev, dtype=torch.float64)
         gathered = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(gathered, mine)
@@ -435,6 +448,7 @@ def main():
         allreduce = {"per_rank_ms_per_step": per_rank, "max_ms_per_step": max(per_rank), "collectives_per_step": n_ar / max(1, args.steps),
                      "backend": backend, "what": "HIP events around the D- and G-gradient flat-bucket all-reduces (6.3 + 4.9 MB fp32) of "
                                                  "every timed step" + ("; gloo: host-side copy time, not a device collective" if backend != "nccl" else "")}
+    if world > 1 and (args.full or args.check_replicas):      # whether the replicas still hold identical weights
         sums = torch.stack([p.detach().double().sum() for p in list(G.parameters()) + list(D.parameters())] +
                            [p.detach().double().abs().sum() for p in list(G.parameters()) + list(D.parameters())])
         lo, hi = sums.clone(), sums.clone()
@@ -456,9 +470,16 @@ def main():
         gemm_how = ("1x v_mfma_f32_*_bf16 per product (bf16 operands, fp32 accumulate)" if bf16 else
                     "3x v_mfma_f32_16x16x32_f16 per product (fp32 operands scaled by a power of two and split hi + lo "
                     "into fp16, fp32 accumulate: fp32-class accuracy, tests/test_hip_kernels.py)")
+
+        def mfma_how(name):
+            if name.startswith("linear_wgrad") and not bf16:
+                return ("3x v_mfma_f32_16x16x32_f16 per product (fp32 operands split hi + lo into fp16 under running "
+                        "power-of-two column scales, fp32 accumulate)")
+            return gemm_how
+
         kernels = {}
         step_bytes = step_floor = 0.0
-        for name in _lib.KERNEL_IDS:
+        for name in (_lib.KERNEL_IDS if args.full else ()):      # the two instrumented steps' table
             n, ms = _lib.prof_read(name)
             nbytes, floor, _ = detail_traffic[name]
             step_bytes += float(nbytes)
@@ -473,12 +494,9 @@ def main():
                 fl = detail_traffic[name][2]
                 if fl:          # GEMM-shaped kernels: flop rate against the MFMA ceiling of their arithmetic
                     tf = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
-                    peak, how = gemm_peak, gemm_how
-                    if name.startswith("linear_wgrad") and not bf16:
-                        how = ("3x v_mfma_f32_16x16x32_f16 per product (fp32 operands split hi + lo into fp16 under running "
-                               "power-of-two column scales, fp32 accumulate)")
+                    peak = gemm_peak
                     kernels[name].update({"achieved_TFLOPs": tf, "mfma_peak_TFLOPs": peak,
-                                          "frac_of_mfma_peak": tf / peak, "mfma": how})
+                                          "frac_of_mfma_peak": tf / peak, "mfma": mfma_how(name)})
                     kernels[name]["bound"] = "hbm" if kernels[name]["frac_of_hbm_peak"] >= tf / peak else "mfma"
                 else:
                     kernels[name]["bound"] = "hbm"
@@ -527,9 +545,9 @@ def main():
             fl = traffic_flops.get(name, 0)
             if fl:      # GEMM-shaped: the MFMA side from the SAME events; the block reports the roof the kernel is closer to
                 tf = fl / (ms * 1e-3) / 1e12
-                peak = kernels.get(name, {}).get("mfma_peak_TFLOPs", gemm_peak)
+                peak = gemm_peak
                 blk.update({"frac_of_mfma_peak": tf / peak, "mfma_peak_TFLOPs": peak, "achieved_TFLOPs": tf,
-                            "mfma": kernels.get(name, {}).get("mfma", gemm_how)})
+                            "mfma": mfma_how(name)})
                 if tf / peak > blk["frac"]:
                     blk.update({"bound": "mfma", "frac_of_hbm_floor": blk["frac"], "achieved_GBps_of_floor": blk["achieved"],
                                 "achieved": tf, "peak": peak, "unit": "TFLOP/s", "frac": tf / peak})
@@ -543,14 +561,15 @@ def main():
                            moved_bytes_per_launch=v["algorithmic_MB_per_launch"] * 1e6, frac_of_moved=v["frac_of_hbm_peak"],
                            share_of_step=v["share_of_step"], measured="instrumented steps after the timed region")
                       for k, v in kernels.items() if k in SHAPES]
-        if args.graph or not blocks:        # --graph: events cannot sit inside a replayed graph
+        if args.graph or not blocks:        # --graph: events cannot sit inside a replayed graph (without --full: no block)
             blocks = all_blocks
         # the block of the kernel the pre-pass ranked first; the instrumented steps after the timed region rank again
         top_all = max(all_blocks, key=lambda b: b["share_of_step"])["kernel"] if all_blocks else None
         dominant = next((b for b in blocks if b["kernel"] == top_key), None) or (
             max(blocks, key=lambda b: b["share_of_step"]) if blocks else {})
-        if dominant:
+        if dominant and top_all is not None:
             dominant["is_time_dominant_edge_kernel"] = bool(top_all == dominant["kernel"])
+        if dominant:
             dominant["chosen_by"] = "largest total HIP-event time among the edge-level profiler keys in one instrumented step before the timed region"
         attention = next((b for b in blocks if b["kernel"] == attn_key), None)
         # HBM bytes per launch from PMC passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in their own runs,
@@ -592,15 +611,8 @@ def main():
                                       "LayerNorm statistics" if bf16 else "fp32"},
             # the time-dominant kernel AND shape of the step (largest share of the timed region among the edge-level
             # kernels), then the attention kernel north_star names
-            "roofline": dominant,
+            "roofline": dominant or None,
             "roofline_attention": attention,
-            # the whole step against the HBM roof: algorithmic bytes of every HIP kernel launch of a step (the per-kernel
-            # formulas of DESIGN.md section 3, accumulated by functional._account) / wall time of two fully instrumented
-            # steps after the timed region
-            "step_hbm": {"algorithmic_GB_per_step": step_bytes / detail_steps / 1e9,
-                         "floor_GB_per_step": step_floor / detail_steps / 1e9,
-                         "achieved_GBps": step_bytes / detail_elapsed / 1e9,
-                         "frac_of_hbm_peak": step_bytes / detail_elapsed / 1e9 / HBM_PEAK_GBS},
             "losses": {"d_loss": d_loss, "g_loss": g_loss},
             "replicas_identical": replicas_identical,
             "allreduce": allreduce,
@@ -610,6 +622,14 @@ def main():
                                    else "the generator runs once per step)"))
                                  if stepper._low_memory(gen_edge) else "fast"),
         }
+        if args.full:
+            # the whole step against the HBM roof: algorithmic bytes of every HIP kernel launch of a step (the per-kernel
+            # formulas of DESIGN.md section 3, accumulated by functional._account) / wall time of two fully instrumented
+            # steps after the timed region
+            out["step_hbm"] = {"algorithmic_GB_per_step": step_bytes / detail_steps / 1e9,
+                               "floor_GB_per_step": step_floor / detail_steps / 1e9,
+                               "achieved_GBps": step_bytes / detail_elapsed / 1e9,
+                               "frac_of_hbm_peak": step_bytes / detail_elapsed / 1e9 / HBM_PEAK_GBS}
         detail = {"kernels": kernels, "roofline_all": all_blocks}
         if captured:
             # two regions of exactly K steps each, `value` = the faster launch mode on this box: K steps launched eagerly (HIP
@@ -632,24 +652,23 @@ def main():
                                    else "eager launches")
         if strict is not None:
             out["strict_f32_hidden"] = strict
-        out["parity_margin"] = parity_margin(dgf.hidden_storage() if not bf16 else "bf16")
-        if world == 1 and args.config == "c2" and act_dtype == "f32" and not args.no_extra and not args.graph:
+        if args.full:
+            out["parity_margin"] = parity_margin(dgf.hidden_storage() if not bf16 else "bf16")
+        if args.full and world == 1 and args.config == "c2" and act_dtype == "f32" and not args.no_extra and not args.graph:
             out["bf16_configs2"] = secondary_bf16_line(dev, G, D, synth, dgf, GANStep, w)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(w, args.cpu_batch, args.cpu_threads)
-        # per-kernel detail: a file, not stdout (round 4's 21 KB line could not be parsed by the driver)
-        detail.update({k: out[k] for k in ("metric", "value", "ms_per_step", "dtype", "config")})
-        name = f"bench_detail_{args.config}_{act_dtype}" + ("" if B == cfg_batch else f"_b{B}") + ".json"
-        written = None
-        for d in (os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")):
+        if args.full:
+            # per-kernel detail: a file in profiles/, not stdout (round 4's 21 KB line could not be parsed by the driver)
+            detail.update({k: out[k] for k in ("metric", "value", "ms_per_step", "dtype", "config")})
+            name = f"bench_detail_{args.config}_{act_dtype}" + ("" if B == cfg_batch else f"_b{B}") + ".json"
+            out["detail_file"] = None
             try:
-                if os.path.isdir(d):
-                    with open(os.path.join(d, name), "w") as f:
-                        json.dump(detail, f, indent=1)
-                    written = written or os.path.relpath(os.path.join(d, name), ROOT)
+                with open(os.path.join(ROOT, "profiles", name), "w") as f:
+                    json.dump(detail, f, indent=1)
+                out["detail_file"] = os.path.join("profiles", name)
             except OSError:
                 pass
-        out["detail_file"] = written
         if dumped is not None:
             dump_outputs(dumped, args.dump_outputs)
 

@@ -152,14 +152,14 @@ def test_low_memory_step_equals_fast_step_at_batch_512():
 def test_bench_n4_gloo_line_on_one_gpu(tmp_path):
     """N > 2 readiness without the hardware: bench.py exactly as the driver's scaling run launches it -- torch.distributed.run,
     four ranks, `--gpus 4` -- with the `gloo` backend and every rank on cuda:0: ONE parseable line with n_gpus = 4, identical
-    replicas and the all-reduce record populated, so that the first real SCALE run cannot die on rendezvous or device-index
+    replicas (`--full`) and the all-reduce record populated, so that the first real SCALE run cannot die on rendezvous or device-index
     plumbing (under `nccl` rank r takes device r: bench.py `dev_index`).  Four ranks, not eight: with the test process and
     the launcher, no more than six processes hold the one GPU."""
     import json
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", DG_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-extra", "--eager", "--batch", "8", "--vertexes", "9", "--depth", "1"]
+           "--full", "--no-cpu-baseline", "--no-extra", "--eager", "--batch", "8", "--vertexes", "9", "--depth", "1"]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1200)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
@@ -439,13 +439,13 @@ def test_two_rank_bench_keeps_replicas_identical(tmp_path):
 def test_bench_n2_line_on_one_gpu_reports_allreduce_time_and_identical_replicas(tmp_path, graph):
     """bench.py --gpus 2 as the driver launches it (torch.distributed.run, one rank per process), with both ranks on
     cuda:0 and the `gloo` backend (DG_DIST_BACKEND: the functional twin of the RCCL run, which needs two GPUs): the line
-    must carry n_gpus = 2, the per-rank time of the two gradient all-reduces per step and replicas_identical = true
-    without any extra flag.  `--graph`: every rank replays its step as three hipGraphs cut at the two all-reduces."""
+    must carry n_gpus = 2, the per-rank time of the two gradient all-reduces per step and, with `--full`, replicas_identical =
+    true.  `--graph`: every rank replays its step as three hipGraphs cut at the two all-reduces."""
     import json
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", DG_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-extra", "--batch", "8", "--vertexes", "9", "--depth", "1"] + (["--graph"] if graph else [])
+           "--full", "--no-cpu-baseline", "--no-extra", "--batch", "8", "--vertexes", "9", "--depth", "1"] + (["--graph"] if graph else [])
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     out = json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][-1])
@@ -453,7 +453,7 @@ def test_bench_n2_line_on_one_gpu_reports_allreduce_time_and_identical_replicas(
     assert out["replicas_identical"] is True
     if graph:
         assert out["config"]["hip_graph_replay"] is True and out["timed_region"].startswith("three hipGraphs")
-    else:      # the default line times the eager launches (`value`) AND, beside them, the three-graph replay
+    else:      # the --full line times the eager launches (`value`) AND, beside them, the three-graph replay
         replay = out["hip_graph_replay_same_step"]
         assert replay["value"] > 0 and out["config"]["hip_graph_replay"] is False and out["timed_region"].startswith("eager launches")
         assert abs(out["value"] - 16 * out["steps"] / (out["ms_per_step"] * out["steps"] / 1e3)) < 1e-3 * out["value"]
@@ -462,13 +462,13 @@ def test_bench_n2_line_on_one_gpu_reports_allreduce_time_and_identical_replicas(
 
 
 def test_bench_line_is_one_short_parseable_record(tmp_path):
-    """The driver stores bench.py's stdout line; round 4's 21 KB line was recorded as unparseable.  The default single-GPU
-    line (with the CPU baseline, the secondary blocks switched off for speed) must be ONE JSON object under 6 KB that
+    """The driver stores bench.py's stdout line; round 4's 21 KB line was recorded as unparseable.  The --full single-GPU
+    line (with the CPU baseline, the bf16 block switched off for speed) must be ONE JSON object under 6 KB that
     carries the contract fields, `roofline` (with its kernel symbol; `frac` = the SURVEY 8d floor bytes -- inputs + outputs of
     the launch -- over the HIP-event time, `frac_of_moved` beside it) and `cpu_baseline`."""
     import json
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "64", "--no-extra",
-           "--cpu-batch", "2"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "64", "--full",
+           "--no-extra", "--cpu-batch", "2"]
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
@@ -533,6 +533,42 @@ def test_bench_dump_outputs_are_reproducible_and_match_the_line(tmp_path):
     assert dumps[0].keys() == dumps[1].keys()
     for k in dumps[0]:
         assert dumps[0][k].dtype == dumps[1][k].dtype and np.array_equal(dumps[0][k], dumps[1][k]), k
+
+
+def test_plain_bench_line_is_the_headline_only_and_dumps_what_full_dumps(tmp_path):
+    """A plain bench.py run measures the headline and nothing beside it: the line carries the contract fields and the roofline
+    blocks of its timed region, none of the --full blocks, and no detail file.  Its timed steps are the --full run's: both dump
+    bit-identical arrays."""
+    import json
+    import numpy as np
+    full_only = ("step_hbm", "hip_graph_replay_same_step", "strict_f32_hidden", "parity_margin", "bf16_configs2", "cpu_baseline",
+                 "detail_file")
+    dumps, lines = {}, {}
+    for run, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-extra"])):
+        d = tmp_path / run
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "8", "--vertexes", "9",
+               "--depth", "1", "--dump-outputs", str(d)] + extra
+        p = subprocess.run(cmd, env=dict(os.environ, DG_FFN_F32="unfused"), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                           timeout=900)
+        assert p.returncode == 0, p.stderr.decode()[-3000:]
+        out_lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
+        assert len(out_lines) == 1 and len(out_lines[0]) < 6144
+        lines[run] = json.loads(out_lines[0])
+        dumps[run] = {f: np.load(d / f) for f in sorted(os.listdir(d))}
+    out = lines["plain"]
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config",
+              "roofline", "losses"):
+        assert k in out, k
+    assert out["unit"] == "molecules/s" and out["higher_is_better"] is True and out["dtype"] == "f32" and out["steps"] == 3
+    assert abs(out["value"] - 8 * 1e3 / out["ms_per_step"]) < 1e-3 * out["value"]
+    assert out["timed_region"] == "eager launches" and out["roofline"]["launches_timed"] > 0
+    assert not [k for k in full_only if k in out] and out["replicas_identical"] is None
+    assert [k for k in full_only if k in lines["full"]] == ["step_hbm", "hip_graph_replay_same_step", "strict_f32_hidden",
+                                                           "parity_margin", "detail_file"]
+    assert out["losses"] == lines["full"]["losses"]
+    assert dumps["plain"].keys() == dumps["full"].keys()
+    for k in dumps["plain"]:
+        assert np.array_equal(dumps["plain"][k], dumps["full"][k]), k
 
 
 def test_dataparallel_replicas_on_one_device_run_the_gradient_penalty():

@@ -327,3 +327,16 @@ def test_bench_dump_outputs_writes_npy_and_samples_over_budget(tmp_path):
         assert np.isin(a, v.reshape(-1)).all(), k
         sizes += os.path.getsize(tmp_path / "a" / f"{k}.npy")
     assert np.load(tmp_path / "a" / "G.w.npy").size < outs["G.w"].size and sizes <= budget
+
+
+def test_bench_full_is_off_by_default(monkeypatch):
+    """bench.py measures only its headline unless --full asks for what lies beside it."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    args = bench.parse()
+    assert not args.full and (args.steps, args.warmup) == (4, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse().full
