@@ -1,14 +1,19 @@
 """Argmax decode on the GPU (reference ``inference.py:197-198``,
 ``src/util/utils.py:220-221``): logits -> compact uint8 label tensors, so the
-CPU-side RDKit ``matrices2mol`` receives bytes instead of float logits."""
+CPU-side RDKit ``matrices2mol`` receives bytes instead of float logits.
+
+``decode_molecule_graphs`` goes the rest of the way to what ``matrices2mol`` (``dataset.py:218-223``) reads: per
+molecule the atom labels, the bond LIST in ``np.nonzero`` order (``start > end``), the connected components and twice
+the valence of every atom -- one launch for the batch (``dg_decode_graph``), one device->host copy (``MoleculeBatch.cpu``)."""
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import _lib
 from .functional import _c, _dev
 
-__all__ = ["argmax_labels", "decode_molecule_labels"]
+__all__ = ["argmax_labels", "decode_molecule_labels", "decode_molecule_graphs", "MoleculeBatch"]
 
 
 def argmax_labels(logits):
@@ -28,3 +33,153 @@ def argmax_labels(logits):
 def decode_molecule_labels(node_sample, edge_sample):
     """(atom labels [B,N], bond labels [B,N,N]) from the Generator's logits."""
     return argmax_labels(node_sample), argmax_labels(edge_sample)
+
+
+# ---- graph decode ---------------------------------------------------------------------------------------------------
+_FIELDS = ("n_bonds", "n_components", "largest", "largest_size", "atoms", "component", "valence2", "bonds")
+
+
+def _layout(B, N, cap, with_valence):
+    """name -> (byte offset, bytes, element bytes, shape) of the packed output buffer, and its size.  Every field starts
+    on a 16-byte boundary, so each is a typed view of the ONE buffer on the device and on the host."""
+    sizes = {"n_bonds": (4, (B,)), "n_components": (4, (B,)), "largest": (4, (B,)), "largest_size": (4, (B,)),
+             "atoms": (1, (B, N)), "component": (1, (B, N)), "valence2": (2, (B, N)), "bonds": (1, (B, cap, 4))}
+    table, off = {}, 0
+    for name in _FIELDS:
+        if name == "valence2" and not with_valence:
+            continue
+        item, shape = sizes[name]
+        nbytes = item * int(np.prod(shape, dtype=np.int64))
+        table[name] = (off, nbytes, item, shape)
+        off += (nbytes + 15) & ~15
+    return table, max(off, 16)
+
+
+_TORCH_TYPES = {1: torch.uint8, 2: torch.uint16, 4: torch.int32}
+_NUMPY_TYPES = {1: np.uint8, 2: np.uint16, 4: np.int32}
+
+
+class MoleculeBatch:
+    """The decoded batch: typed views of one packed byte buffer.
+
+    =============================================  =====================================================================
+    ``atoms``        [B,N]     uint8               atom label per position
+    ``bonds``        [B,cap,4] uint8               ``(start, end, label, 0)`` per bond, ``start > end``, in the order
+                                                   ``zip(*np.nonzero(labels))`` yields them; rows past
+                                                   ``min(n_bonds, cap)`` are unwritten memory
+    ``n_bonds``      [B]       int32               the true bond count (``> cap``: the list was truncated)
+    ``component``    [B,N]     uint8               smallest atom index of the atom's connected component
+    ``n_components``, ``largest``, ``largest_size`` [B] int32   component count; the component with the most atoms
+                                                   (ties: the smaller label) and its atom count
+    ``valence2``     [B,N]     uint16 or None      sum of ``bond_order2[label]`` over the atom's bonds
+    =============================================  =====================================================================
+
+    On the device the fields are ``torch`` tensors.  ``cpu()`` moves the packed buffer with ONE device->host copy and
+    returns a host batch whose fields are ``numpy`` views of it; ``edge_list`` / ``edge_labels`` / ``truncated`` work on
+    the host batch."""
+
+    def __init__(self, buffer, B, N, cap, with_valence):
+        self.buffer, self.B, self.N, self.cap = buffer, B, N, cap
+        self.is_host = isinstance(buffer, np.ndarray)
+        table, total = _layout(B, N, cap, with_valence)
+        assert buffer.shape[0] == total
+        self.valence2 = None
+        for name, (off, nbytes, item, shape) in table.items():
+            part = buffer[off:off + nbytes]
+            view = part.view(_NUMPY_TYPES[item]).reshape(shape) if self.is_host else part.view(_TORCH_TYPES[item]).view(shape)
+            setattr(self, name, view)
+
+    @staticmethod
+    def empty(B, N, cap, with_valence, device):
+        """A device batch over an uninitialised buffer (``decode_molecule_graphs(..., out=)`` fills it)."""
+        _, total = _layout(B, N, cap, with_valence)
+        return MoleculeBatch(torch.empty(total, dtype=torch.uint8, device=device), B, N, cap, with_valence)
+
+    def cpu(self):
+        """The batch on the host: one transfer of the packed buffer for all fields of all molecules."""
+        if self.is_host:
+            return self
+        return MoleculeBatch(self.buffer.cpu().numpy(), self.B, self.N, self.cap, self.valence2 is not None)
+
+    def _host(self, what):
+        if not self.is_host:
+            raise RuntimeError(f"MoleculeBatch.{what} reads the host copy: call .cpu() once for the batch first")
+
+    @property
+    def truncated(self):
+        """Mask [B]: the molecule has more bonds than ``cap`` rows."""
+        return self.n_bonds > self.cap
+
+    def edge_list(self, b):
+        """``(start, end, label)`` triples of molecule ``b`` as an ``[n, 3]`` uint8 array, in ``matrices2mol``'s order."""
+        self._host("edge_list")
+        return self.bonds[b, :min(int(self.n_bonds[b]), self.cap), :3]
+
+    def edge_labels(self, b):
+        """The dense ``[N,N]`` bond-label matrix of molecule ``b`` rebuilt from its list: lower triangle only (what
+        ``matrices2mol`` keeps of the dense argmax), zeros elsewhere."""
+        self._host("edge_labels")
+        e = self.edge_list(b)
+        dense = np.zeros((self.N, self.N), dtype=np.uint8)
+        dense[e[:, 0], e[:, 1]] = e[:, 2]
+        return dense
+
+
+_order2_cache = {}
+
+
+def _order2_table(bond_order2, E, device):
+    if bond_order2 is None:
+        return None
+    if torch.is_tensor(bond_order2):
+        t = bond_order2
+        if t.dtype != torch.uint8 or t.device != device:
+            t = t.to(device=device, dtype=torch.uint8)
+    else:
+        vals = tuple(int(v) for v in bond_order2)
+        if any(v < 0 or v > 255 for v in vals):
+            raise ValueError("bond_order2 holds twice the bond order of every bond label as a byte (0..255)")
+        t = _order2_cache.get((vals, device))      # a host sequence is uploaded once, not at every decode
+        if t is None:
+            if len(_order2_cache) > 64:
+                _order2_cache.clear()
+            t = _order2_cache[(vals, device)] = torch.tensor(vals, dtype=torch.uint8, device=device)
+    if t.dim() != 1 or t.shape[0] != E:
+        raise ValueError(f"bond_order2 needs one entry per bond label ({E}), got shape {tuple(t.shape)}")
+    return _c(t)
+
+
+def decode_molecule_graphs(node_sample, edge_sample, *, bond_order2=None, bond_cap=None, out=None):
+    """Generator logits ``node_sample`` [B,N,M], ``edge_sample`` [B,N,N,E] -> ``MoleculeBatch`` on their device.
+
+    ``bond_order2``: twice the bond order of every bond label (a sequence or uint8 tensor of E entries, e.g.
+    ``[0, 2, 4, 6, 3]`` for no bond / single / double / triple / aromatic) -- asks for ``valence2``.  ``bond_cap``: rows
+    of the bond list per molecule; None = N (N - 1) / 2, which nothing can exceed.  ``out``: a device ``MoleculeBatch``
+    of the same geometry to write into (``MoleculeBatch.empty``) instead of a fresh buffer."""
+    if not (node_sample.is_cuda and edge_sample.is_cuda):
+        raise RuntimeError("druggen_amd.decode runs on the GPU (no CPU fallback)")
+    if node_sample.dim() != 3 or edge_sample.dim() != 4:
+        raise ValueError("decode_molecule_graphs takes node logits [B,N,M] and edge logits [B,N,N,E]")
+    B, N, M = node_sample.shape
+    E = edge_sample.shape[-1]
+    if tuple(edge_sample.shape) != (B, N, N, E) or edge_sample.device != node_sample.device:
+        raise ValueError(f"edge logits {tuple(edge_sample.shape)} do not belong to node logits {tuple(node_sample.shape)}")
+    x, e = _c(node_sample.detach()), _c(edge_sample.detach())
+    cap = N * (N - 1) // 2 if bond_cap is None else int(bond_cap)
+    if cap < 0:
+        raise ValueError("bond_cap must be >= 0")
+    order2 = _order2_table(bond_order2, E, x.device)
+    if out is None:
+        out = MoleculeBatch.empty(B, N, cap, order2 is not None, x.device)
+    elif (out.is_host or (out.B, out.N, out.cap) != (B, N, cap) or (out.valence2 is not None) != (order2 is not None)
+            or out.buffer.device != x.device):
+        raise ValueError("out= must be a device MoleculeBatch of this batch's B, N, bond_cap and valence2 choice")
+    if B == 0:
+        return out
+    with _dev(x):
+        _lib.check(_lib.load().dg_decode_graph(
+            _lib.fptr(x), _lib.fptr(e), None if order2 is None else order2.data_ptr(), B, N, M, E, cap,
+            out.atoms.data_ptr(), out.bonds.data_ptr() if cap > 0 else None, out.n_bonds.data_ptr(),
+            out.component.data_ptr(), out.n_components.data_ptr(), out.largest.data_ptr(), out.largest_size.data_ptr(),
+            None if order2 is None else out.valence2.data_ptr(), _lib.stream_of(x)), "dg_decode_graph")
+    return out

@@ -1,0 +1,119 @@
+"""Molecule sampling: generator forward + graph decode (``dg_decode_graph``), optionally as ONE replayed hipGraph.
+
+The reference's ``inference.py:180-206`` runs the generator eagerly at ``inf_batch_size`` (default 1) -- the
+launch-bound regime -- and pulls dense label matrices to the host per molecule.  ``MoleculeSampler.sample`` returns a
+``decode.MoleculeBatch`` instead: one ``.cpu()`` for the batch, bond lists in ``matrices2mol``'s order.  The capture
+follows ``trainer.GraphedGANStep``: warm-up on a side stream, the packed-weight epoch bumped before and after capture
+(so that the pack kernels are recorded and a replay re-packs from the live parameters), static int32 label buffers for
+one-hot edge batches."""
+from __future__ import annotations
+
+import torch
+
+from .decode import _order2_table, decode_molecule_graphs
+from .functional import (activation_dtype, as_one_hot, attach_one_hot_labels, bump_weights_epoch, one_hot_labels)
+
+__all__ = ["MoleculeSampler"]
+
+
+class MoleculeSampler:
+    """``MoleculeSampler(G, edge, node)`` -- ``edge`` [B,N,N,E], ``node`` [B,N,M]: a batch of the shape to sample at (the
+    generator's input graphs, as ``G(edge, node)`` takes them).
+
+    ``graph=True``: forward and decode are captured once, at construction, into one hipGraph (a single chain of kernels
+    on one stream) at the activation dtype then current, and ``sample`` copies each new batch into static buffers and
+    replays.  Everything ``sample`` returns then lives in static buffers too: the ``MoleculeBatch`` and the logits are
+    OVERWRITTEN by the next ``sample`` -- take ``.cpu()`` (or a clone) before it.  A capture made with a one-hot edge batch
+    embeds edges through their labels and accepts one-hot batches only.  ``graph=False``: the same work, launched eagerly.
+
+    ``G`` runs in ``eval()`` under ``torch.inference_mode()``; its training flags are restored.  In-place weight updates
+    (``load_state_dict``, an optimizer step) are seen by the next ``sample`` in both modes; parameters that were MOVED
+    since the capture (``optim.FlatAdamW`` re-points them into its flat buffer at its first step) make ``sample`` capture
+    again."""
+
+    def __init__(self, G, edge, node, *, graph: bool = True, bond_order2=None, bond_cap=None, warmup: int = 3):
+        if not (edge.is_cuda and node.is_cuda):
+            raise RuntimeError("druggen_amd.sampling runs on the GPU (no CPU fallback)")
+        self.G = G
+        self.bond_cap = bond_cap
+        self._order2 = _order2_table(bond_order2, edge.shape[-1], node.device)      # on the device before any capture
+        self.graph = None
+        self._labels = None
+        if not graph:
+            return
+        self._act_dtype = activation_dtype()
+        self.static_edge, self.static_node = edge.detach().clone(), node.detach().clone()
+        # label buffer of the edge batch: validated HERE, outside the graph (as_one_hot syncs once); None when the capture
+        # batch is not one-hot -- the graph then records the dense embedding kernel and needs no labels
+        lab = one_hot_labels(as_one_hot(edge))
+        if lab is not None:
+            self._labels = lab.clone()
+            attach_one_hot_labels(self.static_edge, self._labels)
+        self._warmup = warmup
+        self._capture()
+
+    def _capture(self):
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):          # warm-up off the default stream: allocator pools, packed weights, scratch
+            for _ in range(self._warmup):
+                self._run(self.static_edge, self.static_node)
+        torch.cuda.current_stream().wait_stream(side)
+        bump_weights_epoch()      # every first use of a weight inside the capture records its pack kernel
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            out = self._run(self.static_edge, self.static_node)
+        bump_weights_epoch()      # cache entries made during capture point into the graph's private pool
+        # the graph reads the parameters where they are NOW: an optimizer that re-points them into a flat buffer at its
+        # first step (optim.FlatAdamW) moves them, and `sample` then captures again
+        self._param_ptrs = [p.data_ptr() for p in self.G.parameters()]
+        self.graph, self._static_out = graph, out
+
+    def _run(self, edge, node):
+        modes = [(m, m.training) for m in self.G.modules()]
+        self.G.eval()
+        try:
+            with torch.inference_mode():
+                _, _, node_sample, edge_sample = self.G(edge, node)
+                batch = decode_molecule_graphs(node_sample, edge_sample, bond_order2=self._order2, bond_cap=self.bond_cap)
+        finally:
+            for m, was in modes:
+                m.training = was
+        return batch, node_sample, edge_sample
+
+    def sample(self, edge, node, *, keep_logits: bool = False, check_one_hot: bool = True):
+        """Decode ``G(edge, node)``: a ``MoleculeBatch``, or ``(batch, node_sample, edge_sample)`` with
+        ``keep_logits=True`` (graphed: views of static buffers, overwritten by the next ``sample``).  A capture made on
+        a one-hot edge batch validates every new edge tensor (one device->host read per new tensor object; labels
+        attached by ``data.load_molecules`` are trusted; ``check_one_hot=False`` skips the check and trusts ``argmax``)."""
+        if self.graph is None:
+            out = self._run(as_one_hot(edge) if check_one_hot else edge, node)
+        else:
+            if tuple(edge.shape) != tuple(self.static_edge.shape) or tuple(node.shape) != tuple(self.static_node.shape):
+                raise RuntimeError(f"MoleculeSampler was captured for edge {tuple(self.static_edge.shape)} / node "
+                                   f"{tuple(self.static_node.shape)}: build a new sampler for another batch shape")
+            if activation_dtype() != self._act_dtype:
+                raise RuntimeError(f"MoleculeSampler was captured with {self._act_dtype} activations: build a new sampler "
+                                   f"after set_activation_dtype")
+            # validate BEFORE touching a static buffer: a rejected batch leaves the dense buffer and its labels consistent
+            lab = None
+            new_edge = edge.data_ptr() != self.static_edge.data_ptr()
+            if new_edge and self._labels is not None:
+                lab = one_hot_labels(as_one_hot(edge)) if check_one_hot else one_hot_labels(edge)
+                if lab is None:
+                    if check_one_hot:
+                        raise RuntimeError("MoleculeSampler was captured with a one-hot edge batch (table-gather embedding); "
+                                           "the new batch is not one-hot: build a sampler on a dense batch for dense inputs")
+                    lab = edge.argmax(-1)
+            if new_edge:
+                self.static_edge.copy_(edge)
+                if lab is not None:
+                    self._labels.copy_(lab)      # in place: the captured kernel reads this buffer
+                    attach_one_hot_labels(self.static_edge, self._labels)
+            if node.data_ptr() != self.static_node.data_ptr():
+                self.static_node.copy_(node)
+            if [p.data_ptr() for p in self.G.parameters()] != self._param_ptrs:
+                self._capture()      # parameters were moved (not just overwritten) since the capture
+            self.graph.replay()
+            out = self._static_out
+        return out if keep_logits else out[0]

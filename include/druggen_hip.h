@@ -578,6 +578,25 @@ int dg_embed_node_bwd(const float* g, const float* a1, const float* a2, const fl
  * [rows, E] -> uint8 labels [rows] (first maximum), so only bytes cross PCIe.      */
 int dg_argmax_decode(const float* logits, int64_t rows, int E, unsigned char* out, dg_stream_t stream);
 
+/* dg_decode_graph: the rest of the reference's decode (inference.py:197-206, dataset.py:218-223) for a whole batch, one
+ * workgroup per molecule (csrc/decode_graph.hip).  node_logits [B,N,M], edge_logits [B,N,N,E] float32, contiguous.  With
+ * a[i] = argmax_m node[b,i,:] and l[i,j] = argmax_e edge[b,i,j,:] (first maximum, NaN maximal: the rule of dg_argmax_decode)
+ * and the undirected graph whose edges are the pairs i > j with l[i,j] != 0 (the upper triangle is never read):
+ *   atoms        [B,N]     u8   a[i]
+ *   bonds        [B,cap,4] u8   (i, j, l[i,j], 0) per edge, ascending i then ascending j -- the order np.nonzero gives after
+ *                               the start > end filter; only the first `cap` are written, the bytes behind them stay untouched
+ *   n_bonds      [B]       i32  the true edge count, also beyond cap
+ *   component    [B,N]     u8   the smallest atom index of i's connected component
+ *   n_components, largest, largest_size [B] i32   component count; the component with the most atoms (ties: the smaller
+ *                               label) and its atom count
+ *   valence2     [B,N]     u16  nullable; sum over i's edges of order2[l] (order2 [E] u8: twice the bond order per label)
+ * All outputs are integer functions of the labels: exact and independent of scheduling.  1 <= N <= 256, 1 <= M, E <= 255,
+ * B >= 0, cap >= 0 (others DG_E_SHAPE); null required pointers, valence2 without order2, bonds == NULL with cap > 0:
+ * DG_E_ARG.  bonds may be NULL when cap == 0.                                                                          */
+int dg_decode_graph(const float* node_logits, const float* edge_logits, const unsigned char* order2, int B, int N, int M,
+                    int E, int cap, unsigned char* atoms, unsigned char* bonds, int* n_bonds, unsigned char* component,
+                    int* n_components, int* largest, int* largest_size, unsigned short* valence2, dg_stream_t stream);
+
 /* ---- opt-in kernel timing with HIP events (bench.py roofline) ----------------
  * dg_prof_enable(mask): bit k of `mask` set = every launch of kernel id k (enum below) is
  * bracketed by two events on the caller's stream (0 = off, -1 = all).  dg_prof_read()
