@@ -120,6 +120,9 @@ SIGNATURES = {
     "dg_adamw_flat_devstep": (c_int, [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float, _P, _P]),
     "dg_argmax_decode": (c_int, [_P, c_int64, c_int, _P, _P]),
     "dg_decode_graph": (c_int, [_P] * 3 + [c_int] * 5 + [_P] * 8 + [_P]),
+    "dg_fp_pack": (c_int, [_P, c_int, c_int64, c_int, _P, _P, _P]),
+    "dg_fp_tanimoto_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "dg_fp_tanimoto": (c_int, [_P, _P, c_int64, _P, _P, c_int64, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "dg_prof_enable": (c_int, [c_int]),
     "dg_prof_reset": (c_int, []),
     "dg_prof_read": (c_int, [c_int, ctypes.POINTER(c_int64), ctypes.POINTER(c_double)]),

@@ -597,6 +597,34 @@ int dg_decode_graph(const float* node_logits, const float* edge_logits, const un
                     int E, int cap, unsigned char* atoms, unsigned char* bonds, int* n_bonds, unsigned char* component,
                     int* n_components, int* largest, int* largest_size, unsigned short* valence2, dg_stream_t stream);
 
+/* ---- Tanimoto similarity of bit fingerprints (csrc/fp_tanimoto.hip; reference src/util/utils.py:550-611,
+ * average_agg_tanimoto / internal_diversity).  Added after DG_VERSION 232 without a version bump.
+ * Packed layout: [n, W] 32-bit words, W = nbits / 32; bit k of a fingerprint is bit k % 32 of word k / 32 (numpy's
+ * packbits(bitorder='little') read as little-endian uint32).  nbits: a multiple of 32 in 32..4096 (others DG_E_SHAPE);
+ * 1024 and 2048 are the specialised cases.  counts [n] i32: the set bits of every row.
+ *
+ * dg_fp_pack: dense [n, nbits] (DG_FP_DENSE_U8: bytes, also torch.bool; DG_FP_DENSE_F32: float32; any element != 0 is a
+ * set bit) -> words [n, W] and counts [n].  n == 0 is a no-op.
+ *
+ * dg_fp_tanimoto: with c = popcount(stock[s] & gen[g]) and q(s, g) = float32(c) / float32(a_s + b_g - c), correctly rounded,
+ * taken as 1 where the denominator is 0, for every gen row g
+ *   DG_FP_MAX : out [G] float32 = max over s of q;  idx [G] i32 (nullable) = the smallest s that attains it
+ *   DG_FP_MEAN: out [G] float64 = (sum over s of q, accumulated in float64) / S;  idx must be NULL
+ * The stock is cut into slices that depend on (S, G) alone; slice results go to `workspace` (dg_fp_tanimoto_workspace_bytes,
+ * 8-byte aligned, may be NULL when that is 0) and a second launch folds them in ascending slice order.  No atomics: the
+ * same bits on every run, stream and device.  Nothing synchronises with the host (capturable in a hipGraph).
+ * S == 0 or G == 0: no-op, returns 0 with `out` untouched.  0 <= S, G < 2^31 (others DG_E_SHAPE); null pointers, an unknown
+ * mode or dtype, misaligned pointers: DG_E_ARG; a workspace that is too small: DG_E_WORKSPACE.                              */
+#define DG_FP_MAX  0
+#define DG_FP_MEAN 1
+#define DG_FP_DENSE_U8  0
+#define DG_FP_DENSE_F32 1
+int    dg_fp_pack(const void* dense, int dtype, int64_t n, int nbits, unsigned* words, int* counts, dg_stream_t stream);
+size_t dg_fp_tanimoto_workspace_bytes(int64_t S, int64_t G);
+int    dg_fp_tanimoto(const unsigned* stock, const int* stock_counts, int64_t S, const unsigned* gen, const int* gen_counts,
+                      int64_t G, int nbits, int mode, void* out, int* idx, void* workspace, size_t workspace_bytes,
+                      dg_stream_t stream);
+
 /* ---- opt-in kernel timing with HIP events (bench.py roofline) ----------------
  * dg_prof_enable(mask): bit k of `mask` set = every launch of kernel id k (enum below) is
  * bracketed by two events on the caller's stream (0 = off, -1 = all).  dg_prof_read()
