@@ -10,7 +10,8 @@ One module per autograd node family, layered (each imports the ones before it; t
 helpers included, so ``druggen_amd.functional.<name>`` resolves whatever module ``<name>`` lives in):
 
     _runtime    shared state: traffic accounting, hidden-tensor storage modes, workspaces, activation dtype, pass flags,
-                reduce-batch / riding-launch scopes, the packed-weight caches' epoch
+                reduce-batch / riding-launch scopes, the packed-weight cache (``PackCache``: one freshness rule, alias
+                resolution, the weights epoch) that every packer below instantiates
     layernorm   residual + LayerNorm and its two backward orders
     dense       nn.Linear: weight gradients, packed weights, row GEMMs with fused prologue / epilogue, q / k / v per launch
     heads       readouts, node embedding chain, Discriminator head

@@ -380,23 +380,125 @@ def _alias_outputs_enabled() -> bool:
     return options.penalty_wgrad == "joined"
 
 
-_pack_cache = {}            # packed weights of the row GEMMs (dense.packed_weight)
-_embed_pack_cache = {}      # packed second layer of the edge embedding (embed._embed_packed_w2)
-_weights_epoch = [0]        # a one-element list: every module that caches packed weights reads the same counter
+# --------------------------------------------------------------------------
+# packed weights: kernels that read a weight in MFMA fragment order keep a packed copy per parameter
+# --------------------------------------------------------------------------
+_alias_canon = {}      # data pointer -> weakref of the parameter an alias output stands for
+
+
+def _weight_alias(t):
+    """A view of parameter ``t`` that a forward node returns as an extra output and hands to its differentiable backward
+    node in place of ``t`` (second-order forward of the gradient penalty): the second-order gradient of the parameter
+    then comes back to the forward node as the gradient of that output and joins the node's own parameter gradient in
+    one multi-tensor add -- otherwise the autograd engine sums the two contributions of every parameter with a launch
+    each (~50 tiny adds per step)."""
+    a = t.view_as(t)
+    with _cache_lock:
+        if len(_alias_canon) > 4096:
+            for k in [k for k, r in list(_alias_canon.items()) if r() is None]:
+                _alias_canon.pop(k, None)
+        _alias_canon[a.data_ptr()] = weakref.ref(t)
+    return a
+
+
+def _canon(w):
+    """The parameter behind an alias made by ``_weight_alias`` (same storage, shape, version), else ``w``: the pack
+    caches are keyed by the parameter object."""
+    r = _alias_canon.get(w.data_ptr())
+    o = r() if r is not None else None
+    if (o is not None and o is not w and o.data_ptr() == w.data_ptr() and o.shape == w.shape and o.stride() == w.stride()
+            and o._version == w._version and o.dtype == w.dtype):
+        return o
+    return w
+
+
+_weights_epoch = [0]                # bumped by writers that change parameters without touching ``tensor._version``
+_pack_caches = weakref.WeakSet()    # every PackCache alive: ``bump_weights_epoch`` sweeps them all
+_EPOCH_SWEEP_ABOVE = 8192           # entries over all caches above which a bump sweeps
+
+
+class _PackEntry:
+    __slots__ = ("refs", "versions", "ptrs", "epoch", "extra", "packed")
+
+    def stamp(self, weights) -> None:
+        self.versions = tuple(w._version for w in weights)
+        self.ptrs = tuple(w.data_ptr() for w in weights)
+        self.epoch = _weights_epoch[0]
+
+
+class PackCache:
+    """Packed copies of one kernel family's weights, keyed by ``(*ids of the weights, *extra)``.  An entry is fresh while
+    every weight is still the same object with the same ``_version`` and ``data_ptr()`` and the weights epoch has not moved;
+    anything else re-makes it.  Touches nothing device-specific: allocation and the pack launch are the caller's ``make``."""
+
+    def __init__(self, limit: int):
+        self.limit = limit      # entries above which a miss first drops those of dead weights (e.g. DataParallel replicas)
+        self._entries = {}
+        _pack_caches.add(self)
+
+    def __len__(self) -> int:
+        return len(self._entries)
+
+    def get(self, weights, extra, make):
+        """The pack of the tuple ``weights`` under the hashable tuple ``extra`` (mode, dtype, ...); ``make(*weights)``
+        builds it on a miss.  Aliases made by ``_weight_alias`` share their parameter's entry."""
+        weights = tuple(map(_canon, weights))
+        key = (*map(id, weights), *extra)
+        e = self._entries.get(key)
+        if e is not None and e.epoch == _weights_epoch[0]:
+            for r, v, p, w in zip(e.refs, e.versions, e.ptrs, weights):
+                if r() is not w or v != w._version or p != w.data_ptr():
+                    break
+            else:
+                return e.packed
+        if len(self._entries) > self.limit:
+            self.sweep()
+        e = _PackEntry()
+        e.refs, e.extra = tuple(weakref.ref(w) for w in weights), extra
+        e.stamp(weights)      # (before make: a writer racing the pack launch leaves the entry stale, not wrongly fresh)
+        e.packed = make(*weights)
+        self._entries[key] = e
+        return e.packed
+
+    def entries(self):
+        """[(key, weights, extra, packed, ptrs)] of the entries whose weights are all alive -- a snapshot; ``ptrs``: the
+        weights' addresses when the entry was made or last restamped."""
+        out = []
+        for key, e in list(self._entries.items()):
+            weights = tuple(r() for r in e.refs)
+            if all(w is not None for w in weights):
+                out.append((key, weights, e.extra, e.packed, e.ptrs))
+        return out
+
+    def restamp(self, key) -> None:
+        """``key``'s pack was refreshed in place from the weights as they are now: the entry is fresh again."""
+        e = self._entries.get(key)
+        weights = () if e is None else tuple(r() for r in e.refs)
+        if e is not None and all(w is not None for w in weights):
+            e.stamp(weights)
+
+    def pop(self, key):
+        e = self._entries.pop(key, None)
+        return None if e is None else e.packed
+
+    def sweep(self) -> None:
+        """Drop the entries of which a weight is dead."""
+        with _cache_lock:
+            for k in [k for k, e in list(self._entries.items()) if any(r() is None for r in e.refs)]:
+                self._entries.pop(k, None)
 
 
 def bump_weights_epoch() -> None:
-    """Invalidate every packed weight (both caches share this epoch).  Called by writers that change
+    """Invalidate every packed weight (every PackCache compares this epoch).  Called by writers that change
     parameters behind autograd's back: ``FlatAdamW.step`` (raw kernel on the flat buffer) and
     ``GraphedGANStep`` (before capture, so that the first use after each optimizer step records its
     pack kernel into the graph, and after every replay, which updates weights without touching
     ``tensor._version``)."""
     _weights_epoch[0] += 1
-    if len(_pack_cache) + len(_embed_pack_cache) > 8192:
-        with _cache_lock:
-            for cache in (_pack_cache, _embed_pack_cache):
-                for k in [k for k, v in list(cache.items()) if v[0]() is None]:
-                    cache.pop(k, None)
+    caches = list(_pack_caches)
+    if sum(len(c) for c in caches) > _EPOCH_SWEEP_ABOVE:
+        for c in caches:
+            c.sweep()
 
 
 __all__ = [_n for _n in dir() if not _n.startswith("__")]

@@ -5,7 +5,6 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import threading
-import weakref
 
 import torch
 from torch.autograd import Function
@@ -523,29 +522,21 @@ class _AttnBlockBwd(Function):
                 None if dy2bar is None else dy2bar.view(dy2_shape), *([None] * 17))
 
 
-_half_pack_cache = {}
+_half_pack_cache = PackCache(1024)
 
 
 def _attn_half_packed(we, woe, dtype):
     """Fragment-order copies of (e.weight, out_e.weight) and their transposes for the fused attention-half kernels
     (dg_attn_half_pack), cached like ``packed_weight``."""
-    key = (id(we), id(woe), dtype)
-    hit = _half_pack_cache.get(key)
-    if (hit is not None and hit[0]() is we and hit[1]() is woe and hit[2] == (we._version, woe._version)
-            and hit[4] == (we.data_ptr(), woe.data_ptr()) and hit[5] == _weights_epoch[0]):
-        return hit[3]
-    if len(_half_pack_cache) > 1024:
-        for k in [k for k, v in _half_pack_cache.items() if v[0]() is None or v[1]() is None]:
-            del _half_pack_cache[k]
-    lib = _lib.load()
-    code = _lib.DTYPES[dtype]
-    packed = torch.empty(int(lib.dg_attn_half_packed_bytes(code)), dtype=torch.uint8, device=we.device)
-    with _dev(we):
-        _lib.check(lib.dg_attn_half_pack(_lib.fptr(_c(we.detach())), _lib.fptr(_c(woe.detach())), packed.data_ptr(), code,
-                                         _lib.stream_of(we)), "dg_attn_half_pack")
-    _half_pack_cache[key] = (weakref.ref(we), weakref.ref(woe), (we._version, woe._version), packed,
-                             (we.data_ptr(), woe.data_ptr()), _weights_epoch[0])
-    return packed
+    def make(we, woe):
+        lib = _lib.load()
+        code = _lib.DTYPES[dtype]
+        packed = torch.empty(int(lib.dg_attn_half_packed_bytes(code)), dtype=torch.uint8, device=we.device)
+        with _dev(we):
+            _lib.check(lib.dg_attn_half_pack(_lib.fptr(_c(we.detach())), _lib.fptr(_c(woe.detach())), packed.data_ptr(), code,
+                                             _lib.stream_of(we)), "dg_attn_half_pack")
+        return packed
+    return _half_pack_cache.get((we, woe), (dtype,), make)
 
 
 def _fused_attn_half_enabled() -> bool:

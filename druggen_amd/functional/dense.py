@@ -5,7 +5,6 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import threading
-import weakref
 
 import torch
 from torch.autograd import Function
@@ -213,35 +212,6 @@ def linear(x, weight, bias=None):
 # --------------------------------------------------------------------------
 # fp32-MFMA row GEMM with fused prologue / epilogue (dg_row_gemm)
 # --------------------------------------------------------------------------
-_alias_canon = {}      # data pointer -> weakref of the parameter an alias output stands for
-
-
-def _weight_alias(t):
-    """A view of parameter ``t`` that a forward node returns as an extra output and hands to its differentiable backward
-    node in place of ``t`` (second-order forward of the gradient penalty): the second-order gradient of the parameter
-    then comes back to the forward node as the gradient of that output and joins the node's own parameter gradient in
-    one multi-tensor add -- otherwise the autograd engine sums the two contributions of every parameter with a launch
-    each (~50 tiny adds per step)."""
-    a = t.view_as(t)
-    with _cache_lock:
-        if len(_alias_canon) > 4096:
-            for k in [k for k, r in list(_alias_canon.items()) if r() is None]:
-                _alias_canon.pop(k, None)
-        _alias_canon[a.data_ptr()] = weakref.ref(t)
-    return a
-
-
-def _canon(w):
-    """The parameter behind an alias made by ``_weight_alias`` (same storage, shape, version), else ``w``: the pack
-    caches are keyed by the parameter object."""
-    r = _alias_canon.get(w.data_ptr())
-    o = r() if r is not None else None
-    if (o is not None and o is not w and o.data_ptr() == w.data_ptr() and o.shape == w.shape and o.stride() == w.stride()
-            and o._version == w._version and o.dtype == w.dtype):
-        return o
-    return w
-
-
 def _join_alias_grads(own, extra):
     """own[i] += extra[i] where both exist (one multi-tensor launch), own[i] = extra[i] where only the latter does."""
     own = list(own)
@@ -261,61 +231,42 @@ def _join_alias_grads(own, extra):
     return own
 
 
+_pack_cache = PackCache(4096)       # (id(w), mode, dtype)
+_pack3_cache = PackCache(1024)      # (id(w0), id(w1), id(w2), mode)
+
+
 def packed_weight(w, mode: int, dtype=torch.float32):
     """MFMA-fragment-ordered copy of an nn.Linear weight (mode 0: forward, 1: input
-    gradient) for activations of ``dtype``, cached per (storage, version): re-packed only after an
+    gradient) for activations of ``dtype``, cached (``PackCache``): re-packed only after an
     optimizer step."""
-    w = _canon(w)
-    key = (id(w), mode, dtype)
-    hit = _pack_cache.get(key)
-    if (hit is not None and hit[0]() is w and hit[1] == w._version and hit[3] == w.data_ptr()
-            and hit[4] == _weights_epoch[0]):
-        return hit[2]
-    if len(_pack_cache) > 4096:       # entries of dead tensors (e.g. DataParallel replicas)
-        with _cache_lock:
-            for k in [k for k, v in list(_pack_cache.items()) if v[0]() is None]:
-                _pack_cache.pop(k, None)
-    lib = _lib.load()
-    rows, cols = w.shape
-    n_out, k = (rows, cols) if mode == 0 else (cols, rows)
-    code = _lib.DTYPES[dtype]
-    packed = torch.empty(int(lib.dg_row_gemm_packed_bytes(n_out, k, code)), dtype=torch.uint8, device=w.device)
-    wd = _c(w.detach())
-    with _dev(w):
-        _lib.check(lib.dg_row_gemm_pack(_lib.fptr(wd), packed.data_ptr(), rows, cols, mode, code, _lib.stream_of(w)),
-                   "dg_row_gemm_pack")
-    _pack_cache[key] = (weakref.ref(w), w._version, packed, w.data_ptr(), _weights_epoch[0])
-    return packed
-
-
-_pack3_cache = {}
+    def make(w):
+        lib = _lib.load()
+        rows, cols = w.shape
+        n_out, k = (rows, cols) if mode == 0 else (cols, rows)
+        code = _lib.DTYPES[dtype]
+        packed = torch.empty(int(lib.dg_row_gemm_packed_bytes(n_out, k, code)), dtype=torch.uint8, device=w.device)
+        wd = _c(w.detach())
+        with _dev(w):
+            _lib.check(lib.dg_row_gemm_pack(_lib.fptr(wd), packed.data_ptr(), rows, cols, mode, code, _lib.stream_of(w)),
+                       "dg_row_gemm_pack")
+        return packed
+    return _pack_cache.get((w,), (mode, dtype), make)
 
 
 def packed_weight3(w0, w1, w2, mode: int):
     """``packed_weight`` for the vertical stack [w0; w1; w2] of three float32 [128,128] weights (q / k / v of an attention
     block) as ONE operand: mode 0 -> the 128 -> 384 forward operand of ``lin3``, mode 1 -> the 384 -> 128 input-gradient
-    operand of ``sum3`` (dg_row_gemm_pack3).  Cached per (storages, versions) like ``packed_weight``."""
-    w0, w1, w2 = _canon(w0), _canon(w1), _canon(w2)
-    key = (id(w0), id(w1), id(w2), mode)
-    ws = (w0, w1, w2)
-    hit = _pack3_cache.get(key)
-    if (hit is not None and all(r() is w for r, w in zip(hit[0], ws)) and hit[1] == tuple(w._version for w in ws)
-            and hit[3] == tuple(w.data_ptr() for w in ws) and hit[4] == _weights_epoch[0]):
-        return hit[2]
-    if len(_pack3_cache) > 1024:
-        with _cache_lock:
-            for k in [k for k, v in list(_pack3_cache.items()) if any(r() is None for r in v[0])]:
-                _pack3_cache.pop(k, None)
-    lib = _lib.load()
-    n_out, k = (384, 128) if mode == 0 else (128, 384)
-    packed = torch.empty(int(lib.dg_row_gemm_packed_bytes(n_out, k, 0)), dtype=torch.uint8, device=w0.device)
-    wd = [_c(w.detach()) for w in ws]
-    with _dev(w0):
-        _lib.check(lib.dg_row_gemm_pack3(_lib.fptr(wd[0]), _lib.fptr(wd[1]), _lib.fptr(wd[2]), packed.data_ptr(), 128, mode, 0,
-                                         _lib.stream_of(w0)), "dg_row_gemm_pack3")
-    _pack3_cache[key] = (tuple(weakref.ref(w) for w in ws), tuple(w._version for w in ws), packed,
-                         tuple(w.data_ptr() for w in ws), _weights_epoch[0])
-    return packed
+    operand of ``sum3`` (dg_row_gemm_pack3).  Cached like ``packed_weight``."""
+    def make(*ws):
+        lib = _lib.load()
+        n_out, k = (384, 128) if mode == 0 else (128, 384)
+        packed = torch.empty(int(lib.dg_row_gemm_packed_bytes(n_out, k, 0)), dtype=torch.uint8, device=ws[0].device)
+        wd = [_c(w.detach()) for w in ws]
+        with _dev(ws[0]):
+            _lib.check(lib.dg_row_gemm_pack3(_lib.fptr(wd[0]), _lib.fptr(wd[1]), _lib.fptr(wd[2]), packed.data_ptr(), 128, mode, 0,
+                                             _lib.stream_of(ws[0])), "dg_row_gemm_pack3")
+        return packed
+    return _pack3_cache.get((w0, w1, w2), (mode,), make)
 
 
 def lin3_supported(x2, ws) -> bool:
@@ -376,22 +327,21 @@ def repack_params(params) -> int:
     if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
         return 0      # the device table is built with a host -> device copy
     ids = {id(p) for p in params}
+
+    def refreshable(ws, ptrs):      # in place: the pack reads the weights where the entry saw them
+        return all(w.is_cuda and w.is_contiguous() for w in ws) and ptrs == tuple(w.data_ptr() for w in ws)
+
     total = 0
     for dtype in (torch.float32, torch.bfloat16):
         entries = []      # (cache, key, weights, packed, mode)
-        for key, hit in _pack_cache.items():
-            if key[0] in ids and key[2] == dtype:
-                w = hit[0]()
-                if (w is not None and w.is_cuda and w.is_contiguous() and hit[3] == w.data_ptr()
-                        and (dtype == torch.float32 or (w.shape[0] % 32 == 0 and w.shape[1] % 32 == 0))):
-                    entries.append((_pack_cache, key, (w,), hit[2], key[1]))
+        for key, ws, (mode, dt), packed, ptrs in _pack_cache.entries():
+            if (id(ws[0]) in ids and dt == dtype and refreshable(ws, ptrs)
+                    and (dtype == torch.float32 or (ws[0].shape[0] % 32 == 0 and ws[0].shape[1] % 32 == 0))):
+                entries.append((_pack_cache, key, ws, packed, mode))
         if dtype == torch.float32:
-            for key, hit in _pack3_cache.items():      # stacks of three weights (q / k / v)
-                if key[0] in ids:
-                    ws = tuple(r() for r in hit[0])
-                    if (all(w is not None and w.is_cuda and w.is_contiguous() for w in ws)
-                            and hit[3] == tuple(w.data_ptr() for w in ws)):
-                        entries.append((_pack3_cache, key, ws, hit[2], key[3]))
+            for key, ws, (mode,), packed, ptrs in _pack3_cache.entries():      # stacks of three weights (q / k / v)
+                if id(ws[0]) in ids and refreshable(ws, ptrs):
+                    entries.append((_pack3_cache, key, ws, packed, mode))
         if len(entries) >= 2:
             total += _repack_entries(entries, dtype)
     return total
@@ -419,12 +369,8 @@ def _repack_entries(entries, dtype) -> int:
         _lib.check(lib.dg_row_gemm_pack_batch(tab.data_ptr(), len(entries),
                                               max(384 if len(ws) == 3 else max(ws[0].shape) for _, _, ws, _, _ in entries),
                                               _lib.DTYPES[dtype], _lib.stream_of(w0)), "dg_row_gemm_pack_batch")
-    for cache, key, ws, packed, _ in entries:
-        if len(ws) == 1:
-            cache[key] = (weakref.ref(ws[0]), ws[0]._version, packed, ws[0].data_ptr(), _weights_epoch[0])
-        else:
-            cache[key] = (tuple(weakref.ref(w) for w in ws), tuple(w._version for w in ws), packed,
-                          tuple(w.data_ptr() for w in ws), _weights_epoch[0])
+    for cache, key, _, _, _ in entries:
+        cache.restamp(key)
     return len(entries)
 
 

@@ -5,7 +5,6 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import threading
-import weakref
 
 import torch
 from torch.autograd import Function
@@ -29,21 +28,22 @@ _ACT_FNS = {"relu": torch.relu, "leaky": lambda t: torch.nn.functional.leaky_rel
             "sigmoid": torch.sigmoid, "tanh": torch.tanh}
 
 
+_embed_pack_cache = PackCache(1024)
+
+
 def _embed_packed_w2(w2, dgrad: bool = False):
-    key = (id(w2), dgrad)
-    hit = _embed_pack_cache.get(key)
-    if (hit is not None and hit[0]() is w2 and hit[1] == w2._version and hit[3] == w2.data_ptr()
-            and hit[4] == _weights_epoch[0]):
-        return hit[2]
-    lib = _lib.load()
-    n_floats = lib.dg_embed_sym_dgrad_packed_floats() if dgrad else lib.dg_embed_sym_packed_floats()
-    packed = torch.empty(int(n_floats), dtype=torch.float32, device=w2.device)
-    wd = _c(w2.detach())
-    with _dev(w2):
-        pack = lib.dg_embed_sym_pack_dgrad if dgrad else lib.dg_embed_sym_pack
-        _lib.check(pack(_lib.ptr(wd), _lib.ptr(packed), _lib.stream_of(w2)), "dg_embed_sym_pack")
-    _embed_pack_cache[key] = (weakref.ref(w2), w2._version, packed, w2.data_ptr(), _weights_epoch[0])
-    return packed
+    """The second layer's weight in the order dg_embed_sym_fwd (``dgrad``: dg_embed_sym_bwd's input gradient) reads it,
+    cached like ``packed_weight``."""
+    def make(w2):
+        lib = _lib.load()
+        n_floats = lib.dg_embed_sym_dgrad_packed_floats() if dgrad else lib.dg_embed_sym_packed_floats()
+        packed = torch.empty(int(n_floats), dtype=torch.float32, device=w2.device)
+        wd = _c(w2.detach())
+        with _dev(w2):
+            pack = lib.dg_embed_sym_pack_dgrad if dgrad else lib.dg_embed_sym_pack
+            _lib.check(pack(_lib.ptr(wd), _lib.ptr(packed), _lib.stream_of(w2)), "dg_embed_sym_pack")
+        return packed
+    return _embed_pack_cache.get((w2,), (dgrad,), make)
 
 
 def _composite_embed_sym(a, w1, b1, w2, b2, act):

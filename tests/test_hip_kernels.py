@@ -1005,14 +1005,42 @@ def test_row_gemm_fused_epilogues(R):
     assert _rel(y, y_ref) < TOL
 
 
-def test_packed_weight_cache_tracks_inplace_updates():
+# every packer of functional/ with the weight shapes it accepts: name -> (shapes of its weights, call on (dgf, weights))
+BF = torch.bfloat16
+PACKERS = {
+    "packed_weight": ([(128, 128)], lambda dgf, ws: dgf.packed_weight(ws[0], 0)),
+    "packed_weight-n384-dgrad": ([(384, 128)], lambda dgf, ws: dgf.packed_weight(ws[0], 1)),
+    "packed_weight-k384-bf16": ([(128, 384)], lambda dgf, ws: dgf.packed_weight(ws[0], 0, BF)),
+    "packed_weight3": ([(128, 128)] * 3, lambda dgf, ws: dgf.packed_weight3(*ws, 0)),
+    "packed_weight3-dgrad": ([(128, 128)] * 3, lambda dgf, ws: dgf.packed_weight3(*ws, 1)),
+    "_embed_packed_w2": ([(128, 64)], lambda dgf, ws: dgf._embed_packed_w2(ws[0])),
+    "_embed_packed_w2-dgrad": ([(128, 64)], lambda dgf, ws: dgf._embed_packed_w2(ws[0], True)),
+    "_attn_half_packed": ([(128, 128)] * 2, lambda dgf, ws: dgf._attn_half_packed(*ws, BF)),
+    "_ffn_packed_f32": ([(384, 128), (128, 384)], lambda dgf, ws: dgf._ffn_packed_f32(*ws)),
+    "_ffn_packed_bf16": ([(384, 128), (128, 384)], lambda dgf, ws: dgf._ffn_packed_bf16(*ws)),
+}
+
+
+@pytest.mark.parametrize("packer", sorted(PACKERS))
+def test_packed_weight_cache_tracks_inplace_updates(packer):
+    """Every packed-weight cache (functional.PackCache behind the six packers): the same tensor while nothing changed; a new
+    pack with other content after an in-place update of ANY of its weights; a new pack with equal content after the weights
+    epoch moved (writers that do not touch ``_version``: the flat AdamW kernel, graph replays)."""
     from druggen_amd import functional as dgf
-    w = torch.randn(128, 128, device="cuda")
-    p1 = dgf.packed_weight(w, 0)
-    assert dgf.packed_weight(w, 0) is p1
-    w.add_(1.0)                                    # what an optimizer step does
-    p2 = dgf.packed_weight(w, 0)
-    assert p2 is not p1 and not torch.equal(p1, p2)
+    shapes, pack = PACKERS[packer]
+    ws = [(_gen(shape, 700 + i) * 0.1).float().cuda() for i, shape in enumerate(shapes)]
+    p1 = pack(dgf, ws)
+    assert pack(dgf, ws) is p1
+    for w in ws:
+        w.add_(1.0)                                    # what an optimizer step does
+        p2 = pack(dgf, ws)
+        assert p2 is not p1 and not torch.equal(p1, p2)
+        assert pack(dgf, ws) is p2
+        p1 = p2
+    dgf.bump_weights_epoch()
+    p3 = pack(dgf, ws)
+    assert p3 is not p1 and p3.data_ptr() != p1.data_ptr() and torch.equal(p3, p1)
+    assert pack(dgf, ws) is p3
 
 
 @pytest.mark.parametrize("hidden", ["f32", "dh16"])
