@@ -116,6 +116,7 @@ SIGNATURES = {
     "dg_onehot_embed_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "dg_onehot_embed_bwd": (c_int, [_P, _P, _P, _P, c_size_t, c_int, c_int, c_int, c_int, c_int, _P]),
     "dg_densify": (c_int, [_P, _P, _P, c_int64, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "dg_mol_gather": (c_int, [_P, _P, _P, c_int64, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "dg_adamw_flat": (c_int, [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float, c_int64, _P]),
     "dg_adamw_flat_devstep": (c_int, [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float, _P, _P]),
     "dg_argmax_decode": (c_int, [_P, c_int64, c_int, _P, _P]),

@@ -515,6 +515,30 @@ int dg_onehot_embed_bwd(const int* labels, const void* g, float* dtable, void* w
 int dg_densify(const int64_t* edge_src, const int64_t* edge_dst, const int64_t* edge_attr, int64_t n_edges,
                int B, int N, int E, int* labels, float* a, int* bad_count, dg_stream_t stream);
 
+/* dg_mol_gather: the same batch -- labels, `a`, and the node one-hots `x` of reference utils.py:128-142 -- assembled from a
+ * molecule set that STAYS on the device, by index (csrc/mol_gather.hip, druggen_amd/resident.py).  Added after DG_VERSION 232
+ * without a version bump.  The store, n molecules padded to N atoms:
+ *   atoms   [n, N]  u8   atom label per position (PAD = 0), each < M
+ *   ptr     [n + 1] i64  ptr[m] .. ptr[m + 1]: molecule m's slice of `entries`
+ *   entries         u32  one word per NON-ZERO of the molecule's dense [N, N] bond-label matrix:
+ *                        row | col << 8 | label << 16 (bits 24-31 zero) -- the directed entries to_dense_adj would scatter, so
+ *                        a symmetric molecule stores both directions.  Within a molecule the (row, col) pairs are unique,
+ *                        row, col < N and 1 <= label < E: the builder (ResidentMolecules.pack) sums duplicates and validates,
+ *                        so the kernel has no out-of-range counter for labels.  A word that breaks row, col < N is skipped.
+ * For b < B and m = index[b] (i64, device; repeats allowed):
+ *   labels [B, N, N]    i32  the dense bond labels of molecule m
+ *   a      [B, N, N, E] f32  one-hot of labels over the last dim
+ *   x      [B, N, M]    f32  one-hot of atoms[m, :]
+ * EVERY element of the three outputs is written, zeros included (no memset by the caller); the molecule bases need only
+ * 4-byte alignment.  An index outside [0, n) is clamped into range (every access stays in bounds) and counted in `bad_index`
+ * (1 int32, device), which the call zeroes first (a memset node on `stream`).  The number of entries read per molecule is
+ * clamped to N N.  One workgroup per output molecule; nothing synchronises with the host (capturable in a hipGraph); the
+ * outputs are exact 0 / 1 and integers, identical to dg_densify's for the same molecules.
+ * 1 <= N <= 256, 1 <= M <= 255, 1 <= E <= 16, B >= 0, n >= 0 (n >= 1 when B > 0): others DG_E_SHAPE; B == 0 returns 0
+ * without a launch; null or misaligned pointers: DG_E_ARG.                                                                */
+int dg_mol_gather(const uint8_t* atoms, const int64_t* ptr, const uint32_t* entries, int64_t n, const int64_t* index, int B,
+                  int N, int M, int E, float* a, int* labels, float* x, int* bad_index, dg_stream_t stream);
+
 /* dg_adamw_flat: one torch.optim.AdamW update (reference train.py:213-214,368,384;
  * decoupled weight decay, no amsgrad) over flat float32 buffers; `step` >= 1.       */
 int dg_adamw_flat(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
