@@ -43,9 +43,6 @@ constexpr int kSecOET = 2 * kSec;             // Woe^T       (ds = dz4 Woe)
 constexpr int kSecET = 3 * kSec;              // We^T        (dy = de We)
 constexpr float kNegBig = -3.0e38f;
 
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 __device__ __forceinline__ float vmax(float a, float b) {   // plain v_max_f32 (fmaxf adds a canonicalising v_max per operand)
     float r;
     asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
@@ -57,17 +54,6 @@ __device__ __forceinline__ float xor_vmax16(float x) {     // max over lane bits
     r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return vmax(__uint_as_float(r[0]), __uint_as_float(r[1]));
 }
-// Workgroup barrier that orders LDS traffic only: the kernels below wait for their LDS-DMA BEFORE issuing a tile's
-// global stores (the DMA of the next tile was issued a whole tile earlier, so that wait is free), and must not sit on
-// `vmcnt(0)` at the next barrier until those stores have been acknowledged (PMC: waves parked > 50 % of their cycles).
-// (The two empty asm statements are COMPILER barriers: s_barrier is IntrNoMem for LLVM, which is otherwise free to move
-// LDS loads / stores across it.)
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0); vmcnt / expcnt untouched
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 constexpr float kLog2e = 1.4426950408889634f;
 // two-wide fp32 arithmetic: hipcc maps <2 x float> mul / add / fma to v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 (one
 // issue slot for two lanes' worth of work) -- the fused kernels are VALU-issue bound, not MFMA or HBM bound
@@ -76,13 +62,7 @@ __device__ __forceinline__ f32x2 lo2(f32x4 v) { return f32x2{v[0], v[1]}; }
 __device__ __forceinline__ f32x2 hi2(f32x4 v) { return f32x2{v[2], v[3]}; }
 __device__ __forceinline__ f32x2 bc2(float x) { return f32x2{x, x}; }
 __device__ __forceinline__ f32x2 unpack2_bf16(unsigned w) { return f32x2{lo_bf16(w), hi_bf16(w)}; }
-__device__ __forceinline__ float sum16(float x) {      // sum over the 16 lanes of a DPP row, result in all 16
-    x = dpp_add<0xB1>(x);
-    x = dpp_add<0x4E>(x);
-    x = dpp_add<0x141>(x);
-    x = dpp_add<0x140>(x);
-    return x;
-}
+__device__ __forceinline__ float sum16(float x) { return row16_sum(x); }      // (lane_reduce.h, through gemm_bf16.h)
 __device__ __forceinline__ u32x4_t pack8_bf16(float4 a, float4 b) {
     u32x4_t o;
     o[0] = pack_bf16(a.x, a.y); o[1] = pack_bf16(a.z, a.w);
@@ -446,10 +426,6 @@ __device__ __forceinline__ u32x2_t tr_read(unsigned addr) {
 template <int YOUNGER>
 __device__ __forceinline__ void tr_wait(u32x2_t (&r)[4]) {
     asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]) : "n"(YOUNGER));
-}
-__device__ __forceinline__ bf16x8 cat8(u32x2_t lo, u32x2_t hi) {
-    const u32x4_t t = {lo[0], lo[1], hi[0], hi[1]};
-    return __builtin_bit_cast(bf16x8, t);
 }
 // acc[n] += A^T B over the MB 16-row blocks of one tile, n = 0..7 (16 output columns each): A operands `aop` straight from
 // the attention-layout registers, B operands by ds_read_b64_tr_b16 from the row-major tile at `tb` (this lane's source

@@ -23,6 +23,8 @@
 // of the first half through a 1.5 KB LDS stash and the second half finishes o_i.  k_j / v_j are fetched per stage there
 // (two register sets do not fit next to the two weights' fragments).
 #include "common.h"
+#include "lane_reduce.h"
+#include "mfma_f16.h"
 #include "traversal.h"
 
 #ifndef AH_DBG
@@ -30,13 +32,6 @@
 #endif                // -> HBM / planes, 8 no finish (residual, LayerNorm, stores), 16 no q / k / v loads, 32 no y split
 namespace dg {
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kNP = 48;                                   // rows of a stage (row groups are padded to 48 rows)
 constexpr int kPlane = 16 * kNP * 16;                     // [k-step 4][k-quarter 4][row 48 (xor-swizzled)][16 B]
@@ -50,49 +45,6 @@ constexpr int kOffRun = kOffO + 512;                      // two-stage row group
 constexpr int kLds = kOffRun + 3 * 512;
 constexpr int kCons = 8, kProd = 4;
 constexpr float kNegBig = -3.0e38f;
-
-template <int CTRL>
-__device__ __forceinline__ unsigned umax_dpp(unsigned x) {
-    const unsigned moved = static_cast<unsigned>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), CTRL, 0xF, 0xF, true));
-    return x > moved ? x : moved;
-}
-template <int CTRL>
-__device__ __forceinline__ float sum_dpp(float x) {
-    return x + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, true));
-}
-template <int CTRL>
-__device__ __forceinline__ float max_dpp(float x) {
-    return fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, true)));
-}
-// over the 16 lanes of a DPP row, result in every lane (quad xor 1, quad xor 2, half-row mirror, row mirror)
-__device__ __forceinline__ float row16_sum(float x) {
-    x = sum_dpp<0xB1>(x);
-    x = sum_dpp<0x4E>(x);
-    x = sum_dpp<0x141>(x);
-    return sum_dpp<0x140>(x);
-}
-__device__ __forceinline__ float row16_max(float x) {
-    x = max_dpp<0xB1>(x);
-    x = max_dpp<0x4E>(x);
-    x = max_dpp<0x141>(x);
-    return max_dpp<0x140>(x);
-}
-// sum over the 32 lanes of a half-wave, result in every lane: the two 16-lane row totals meet through one v_permlane16_swap
-// (four v_readlane + their wait states before)
-__device__ __forceinline__ float half_wave_total(float x) {
-    x = row16_sum(x);
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-// in-place MFMAs and the fence in front of the first vector read of their results: see row_gemm_k384.hip
-__device__ __forceinline__ void mfma16(f32x4& acc, const f16x8& a, const f16x8& b) {
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void mfma16_first(f32x4& acc, const f16x8& a, const f16x8& b) {
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void mfma_results_ready() { asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); }
 
 struct HalfArgs {
     const float* y;       // [B,N,N,128]
@@ -319,9 +271,9 @@ __global__ __launch_bounds__(64 * (kCons + kProd)) void attn_half_f32_fwd_kernel
                 float4 v = *reinterpret_cast<const float4*>(smem + kOffTo + trow + i * 4096);
                 v += res[i];
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rp, voff, i * 4096, 0);
-                const float mu = half_wave_total((v.x + v.y) + (v.z + v.w)) * (1.0f / 128.0f);
+                const float mu = half_wave_total_swap((v.x + v.y) + (v.z + v.w)) * (1.0f / 128.0f);
                 const float4 d = v - f4(mu);
-                const float var = half_wave_total((d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w)) * (1.0f / 128.0f);
+                const float var = half_wave_total_swap((d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w)) * (1.0f / 128.0f);
                 const float rsd = rsqrtf(var + a.eps);
                 v = fma4(rsd * d, gam, bet);
                 const unsigned soff = l32 == 0 ? static_cast<unsigned>(row) * 4u : 0x7FFFFFF0u;      // one lane per row

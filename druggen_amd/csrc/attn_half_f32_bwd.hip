@@ -17,19 +17,14 @@
 //   ONE barrier per row group: planes, e tile and de tile are double-buffered (155 KB of LDS).
 // The second part -- dy = de We + dz4 (+ the previous block's LayerNorm backward) -- stays dg_row_gemm / dg_row_gemm_ln_bwd.
 #include "common.h"
+#include "lane_reduce.h"
+#include "mfma_f16.h"
 #include "traversal.h"
 
 namespace dg {
 bool reduce_batch_try_add(const float* part, int S, long long n_floats, float* out);      // linear_wgrad.hip
 void launch_ln_finish(const float* part, int nblocks, int K, int C, float* out0, float* out1, hipStream_t stream);
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kNP = 48;                                   // rows of a stage (row groups are padded to 48 rows)
 constexpr int kPlane = 16 * kNP * 16;                     // [k-step 4][k-quarter 4][row 48 (xor-swizzled)][16 B]
@@ -45,50 +40,9 @@ constexpr int kLds = kOffRed + 8 * 2 * 512;
 constexpr int kCons = 8, kProd = 4;
 constexpr float kNegBig = -3.0e38f;
 
-template <int CTRL>
-__device__ __forceinline__ unsigned umax_dpp(unsigned x) {
-    const unsigned moved = static_cast<unsigned>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), CTRL, 0xF, 0xF, true));
-    return x > moved ? x : moved;
-}
-template <int CTRL>
-__device__ __forceinline__ float sum_dpp(float x) {
-    return x + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, true));
-}
-template <int CTRL>
-__device__ __forceinline__ float max_dpp(float x) {
-    return fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, true)));
-}
-// over the 16 lanes of a DPP row, result in every lane (quad xor 1, quad xor 2, half-row mirror, row mirror)
-__device__ __forceinline__ float row16_sum(float x) {
-    x = sum_dpp<0xB1>(x);
-    x = sum_dpp<0x4E>(x);
-    x = sum_dpp<0x141>(x);
-    return sum_dpp<0x140>(x);
-}
-__device__ __forceinline__ float row16_max(float x) {
-    x = max_dpp<0xB1>(x);
-    x = max_dpp<0x4E>(x);
-    x = max_dpp<0x141>(x);
-    return max_dpp<0x140>(x);
-}
 __device__ __forceinline__ float4 row16_sum4(float4 v) {
     return make_float4(row16_sum(v.x), row16_sum(v.y), row16_sum(v.z), row16_sum(v.w));
 }
-// sum over the 32 lanes of a half-wave, result in every lane
-__device__ __forceinline__ float half_wave_total(float x) {
-    x = row16_sum(x);
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-// in-place MFMAs and the fence in front of the first vector read of their results: see row_gemm_k384.hip
-__device__ __forceinline__ void mfma16(f32x4& acc, const f16x8& a, const f16x8& b) {
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void mfma16_first(f32x4& acc, const f16x8& a, const f16x8& b) {
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void mfma_results_ready() { asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); }
 
 struct HalfBwdArgs {
     const float* dy2;     // [B,N,N,128]
@@ -230,8 +184,8 @@ __global__ __launch_bounds__(64 * (kCons + kProd)) void attn_half_f32_bwd1_kerne
                 const float4 xh = rsd * (prr[i] - f4(mu));
                 const float4 g = dyr[i];
                 const float4 u = g * gam;
-                const float c1 = half_wave_total((u.x + u.y) + (u.z + u.w)) * (1.0f / 128.0f);
-                const float c2 = half_wave_total((u.x * xh.x + u.y * xh.y) + (u.z * xh.z + u.w * xh.w)) * (1.0f / 128.0f);
+                const float c1 = half_wave_total_swap((u.x + u.y) + (u.z + u.w)) * (1.0f / 128.0f);
+                const float c2 = half_wave_total_swap((u.x * xh.x + u.y * xh.y) + (u.z * xh.z + u.w * xh.w)) * (1.0f / 128.0f);
                 dgam = fma4(livef * g, xh, dgam);      // (g = 0 in the padding rows)
                 dbet += livef * g;
                 dzr[i] = (hw + 8 * i < N) ? rsd * (u - f4(c1) - c2 * xh) : f4(0.f);

@@ -4,6 +4,7 @@
 //   * argmax decode  -- reference inference.py:197-198 (torch.max(.., -1)[1])
 // All HBM/latency-bound byte and elementwise work: one coalesced pass each.
 #include "bf16.h"
+#include "lane_reduce.h"
 
 namespace dg {
 namespace {
@@ -117,17 +118,7 @@ __global__ void argmax_kernel(const float* __restrict__ logits, int64_t rows, in
 // y[r][n] = sum_k x[r][k] w[n][k] + b[n]: a coalesced stream over x (32 lanes x 4 columns = one 128-wide row, two rows
 // per wave instruction), N x 4 multiply-adds per lane against weights held in registers, a 32-lane DPP sum per output.
 // x may be float32 or bfloat16 (the activation dtype); the logits are float32 in every mode (no `.float()` copy).
-__device__ __forceinline__ float half_wave_sum32(float x) {
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x141, 0xF, 0xF, true));   // row_half_mirror
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x140, 0xF, 0xF, true));   // row_mirror
-    const float lo = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 0));
-    const float hi = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 16));
-    const float lo2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 32));
-    const float hi2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 48));
-    return (threadIdx.x & 32) ? lo2 + hi2 : lo + hi;
-}
+__device__ __forceinline__ float half_wave_sum32(float x) { return half_wave_total_readlane(x, threadIdx.x & 32); }
 template <typename T, int NMAX>
 __global__ __launch_bounds__(256) void skinny_linear_fwd_kernel(const T* __restrict__ x, const float* __restrict__ w,
                                                               const float* __restrict__ b, float* __restrict__ y,

@@ -32,26 +32,14 @@ constexpr int kC = 128, kH = 64, kEP = 8;
 constexpr int kHalf = kH * kEP + kH;           // dW1 [64][8] + db1 [64] of one wave half
 constexpr int kSmall = 2 * kHalf + kC;         // per-block partials: two halves (waves 0..3 / 4..7), then db2 [128]
 
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ bf16x8 cat8(u32x2_t lo, u32x2_t hi) {
-    const u32x4_t t = {lo[0], lo[1], hi[0], hi[1]};
-    return __builtin_bit_cast(bf16x8, t);
-}
 // swizzle of the [rows][128] tiles (256-byte pitch): see bswz in attn_half.hip
 __device__ __forceinline__ int swz16(int row) {
     const int r = row & 15;
     const int p = (r & 3) | ((((r >> 2) ^ (r >> 3)) & 1) << 2);
     return (p << 1) | (r >> 3);
 }
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0)
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-// ds_read_b64_tr_b16 (compiler builtin: tracked by hipcc's scoreboard)
+// ds_read_b64_tr_b16 (compiler builtin: tracked by hipcc's scoreboard; attn_half.hip issues its own from inline asm with an
+// immediate offset and explicit waits)
 __device__ __forceinline__ u32x2_t tr_read(unsigned addr) {
     typedef short s16x4 __attribute__((ext_vector_type(4)));
     typedef __attribute__((address_space(3))) s16x4 lds_s16x4;

@@ -50,9 +50,6 @@ constexpr int kTPitch = 144;                      // bytes per channel row of a 
                                                   // 32 consecutive channels hit 16 distinct 16-byte slots twice)
 constexpr int kTBytes = kH * kTPitch;             // 54 KB
 
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 __device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
@@ -160,9 +157,9 @@ __device__ __forceinline__ f32x4 gemm_down_block16(const char* tile, int rb, con
 //     reductions are 3 DPP steps inside a half-row (no readlane), and the results leave as 16-byte stores;
 //   * outputs are stored unconditionally (the caller pads them to whole tiles): no per-row branches.
 __device__ __forceinline__ float sum8(float x) {      // sum over the 8 lanes of a half-row, result in all 8
-    x = dpp_add<0xB1>(x);    // quad_perm [1,0,3,2]
-    x = dpp_add<0x4E>(x);    // quad_perm [2,3,0,1]
-    x = dpp_add<0x141>(x);   // row_half_mirror: lane i <-> 7 - i, i.e. the other quad
+    x = sum_dpp<0xB1>(x);    // quad_perm [1,0,3,2]
+    x = sum_dpp<0x4E>(x);    // quad_perm [2,3,0,1]
+    x = sum_dpp<0x141>(x);   // row_half_mirror: lane i <-> 7 - i, i.e. the other quad
     return x;
 }
 template <bool SAVE>

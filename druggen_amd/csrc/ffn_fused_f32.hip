@@ -29,6 +29,7 @@
 //     permutation is applied on the SOURCE address); waits are counted s_waitcnt vmcnt(N) with N derived from the fixed
 //     issue order below (a store's acknowledgement is never waited for inside a pass).
 #include "common.h"
+#include "f16_scale.h"
 
 #include "pair.h"
 #include "traversal.h"
@@ -44,11 +45,6 @@
 namespace dg {
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #ifndef FF_AUX
 #define FF_AUX 0      // cache-policy bits of the result stores (gfx950 buffer stores: 1 sc0, 2 nt, 16 sc1)
 #endif
@@ -83,39 +79,22 @@ constexpr int kOffBits = kOffTab + 1408 * 4;     // ReLU mask words of the pass:
 constexpr int kLds = kOffBits + 4 * 512 * 4;
 static_assert(kLds <= 160 * 1024, "LDS budget");
 
-// acc += A . B on v_mfma_f32_16x16x32_f16, ALWAYS in place; the first MFMA of a chain takes the constant 0; a vector read of
-// a result is fenced: see row_gemm_k384.hip (a renamed destination one slot behind its producer read a partly written
-// accumulator on gfx950).
-__device__ __forceinline__ void mfma16(f32x4& acc, const f16x8& a, const f16x8& b) {
+// the in-place MFMAs of mfma_f16.h behind this file's ablation gate (FF_DBG & 1: no MFMAs)
+__device__ __forceinline__ void ff_mfma16(f32x4& acc, const f16x8& a, const f16x8& b) {
     if (FF_DBG & 1) {
         asm volatile("" : "+v"(acc) : "v"(a), "v"(b));
         return;
     }
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
+    mfma16(acc, a, b);
 }
-__device__ __forceinline__ void mfma16_first(f32x4& acc, const f16x8& a, const f16x8& b) {
+__device__ __forceinline__ void ff_mfma16_first(f32x4& acc, const f16x8& a, const f16x8& b) {
     if (FF_DBG & 1) {
         acc = f32x4{0.f, 0.f, 0.f, 0.f};
         asm volatile("" : "+v"(acc) : "v"(a), "v"(b));
         return;
     }
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(b));
+    mfma16_first(acc, a, b);
 }
-__device__ __forceinline__ void mfma_results_ready() { asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); }
-
-// packed fp16 pair { fp16(s0 - hi.lo), fp16(s1 - hi.hi) }: the lo plane of two scaled values whose hi plane is `hpk`
-__device__ __forceinline__ unsigned lo_pair(unsigned hpk, float s0, float s1) {
-    unsigned d;
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hpk), "v"(s0));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(d) : "v"(hpk), "v"(s1));
-    return d;
-}
-__device__ __forceinline__ unsigned scale_exponent(float absmax) {      // biased exponent, clamped away from 0
-    const unsigned e = __float_as_uint(absmax) >> 23;
-    return e < 15u ? 15u : e;
-}
-__device__ __forceinline__ float scale_of(unsigned e) { return __uint_as_float((268u - e) << 23); }      // 2^(14 - (e - 127))
-__device__ __forceinline__ float inv_scale_of(unsigned e) { return __uint_as_float((e - 14u) << 23); }
 
 // hi / lo fp16 planes of eight values under the scale sc: (x sc) = hi + lo up to 2^-22 of the row maximum
 __device__ __forceinline__ void split8(const float (&v)[8], float sc, f16x8& hi, f16x8& lo) {
@@ -464,16 +443,16 @@ __global__ __launch_bounds__(64 * kWaves) void ffn_fused_f32_kernel(const FProb 
                 const f16x8 &wha = fr[ks & 1][0], &wla = fr[ks & 1][1], &whb = fr[ks & 1][2], &wlb = fr[ks & 1][3];
                 f32x4 &ca = a[ks & 1], &cb = a[2 + (ks & 1)];
                 if (ks < 2) {
-                    mfma16_first(ca, wla, xh[ks]);
-                    mfma16_first(cb, wlb, xh[ks]);
+                    ff_mfma16_first(ca, wla, xh[ks]);
+                    ff_mfma16_first(cb, wlb, xh[ks]);
                 } else {
-                    mfma16(ca, wla, xh[ks]);
-                    mfma16(cb, wlb, xh[ks]);
+                    ff_mfma16(ca, wla, xh[ks]);
+                    ff_mfma16(cb, wlb, xh[ks]);
                 }
-                mfma16(ca, wha, xl[ks]);
-                mfma16(cb, whb, xl[ks]);
-                mfma16(ca, wha, xh[ks]);
-                mfma16(cb, whb, xh[ks]);
+                ff_mfma16(ca, wha, xl[ks]);
+                ff_mfma16(cb, whb, xl[ks]);
+                ff_mfma16(ca, wha, xh[ks]);
+                ff_mfma16(cb, whb, xh[ks]);
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (FF_PROF) {
@@ -585,13 +564,13 @@ __global__ __launch_bounds__(64 * kWaves) void ffn_fused_f32_kernel(const FProb 
                 __builtin_amdgcn_sched_barrier(0);
                 const f16x8 &wh = fr[j % 3][0], &wl = fr[j % 3][1];
                 if (j == 0) {
-                    mfma16_first(q[0], wl, hh[0]);
-                    mfma16_first(q[1], wh, hl[0]);
-                    mfma16_first(q[2], wh, hh[0]);
+                    ff_mfma16_first(q[0], wl, hh[0]);
+                    ff_mfma16_first(q[1], wh, hl[0]);
+                    ff_mfma16_first(q[2], wh, hh[0]);
                 } else {
-                    mfma16(q[0], wl, hh[j]);
-                    mfma16(q[1], wh, hl[j]);
-                    mfma16(q[2], wh, hh[j]);
+                    ff_mfma16(q[0], wl, hh[j]);
+                    ff_mfma16(q[1], wh, hl[j]);
+                    ff_mfma16(q[2], wh, hh[j]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }

@@ -16,6 +16,7 @@
 #pragma once
 
 #include "bf16.h"
+#include "lane_reduce.h"
 
 namespace dg {
 
@@ -52,22 +53,27 @@ __device__ __forceinline__ void dma_tile_bf16(const bf16_t* __restrict__ a, int6
     }
 }
 
-// ---- sum over the 32 lanes of a half-wave (DPP inside 16-lane rows + two scalar reads) -----------
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float x) {
-    const int moved = __builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, true);
-    return x + __int_as_float(moved);
+// sum over the 32 lanes of a half-wave, result in every lane (lane_reduce.h)
+__device__ __forceinline__ float half_wave_sum(float x) { return half_wave_total_readlane(x, threadIdx.x & 32); }
+
+// ---- the bf16 MFMA, operand concatenation and LDS-only barrier of attn_half.hip, embed_bf16.hip, ffn_bf16.hip ----------
+__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
-__device__ __forceinline__ float half_wave_sum(float x) {
-    x = dpp_add<0xB1>(x);    // quad_perm [1,0,3,2]
-    x = dpp_add<0x4E>(x);    // quad_perm [2,3,0,1]
-    x = dpp_add<0x141>(x);   // row_half_mirror
-    x = dpp_add<0x140>(x);   // row_mirror: every lane holds its 16-lane row total
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 0));
-    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 32));
-    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 48));
-    return (threadIdx.x & 32) ? r2 + r3 : r0 + r1;
+__device__ __forceinline__ bf16x8 cat8(u32x2_t lo, u32x2_t hi) {
+    const u32x4_t t = {lo[0], lo[1], hi[0], hi[1]};
+    return __builtin_bit_cast(bf16x8, t);
+}
+// Workgroup barrier that orders LDS traffic only: the kernels below wait for their LDS-DMA BEFORE issuing a tile's
+// global stores (the DMA of the next tile was issued a whole tile earlier, so that wait is free), and must not sit on
+// `vmcnt(0)` at the next barrier until those stores have been acknowledged (PMC: waves parked > 50 % of their cycles).
+// (The two empty asm statements are COMPILER barriers: s_barrier is IntrNoMem for LLVM, which is otherwise free to move
+// LDS loads / stores across it.)
+__device__ __forceinline__ void lds_barrier() {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0); vmcnt / expcnt untouched
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
 }
 
 // ---- fp32 exchange tile [64][N]: accumulators (a lane owns 4 consecutive channels of a row) go in

@@ -6,17 +6,18 @@
 //     dW[n][k] = sum_r dy[r][n] * x[r][k]        db[n] = sum_r dy[r][n]
 //
 // with R = B*N*N (518 400 at configs[1]) and N,K in {64,128,384}: a tall-skinny
-// "TN" GEMM whose contraction runs over the huge row dimension.  fp32 MFMA
-// (v_mfma_f32_32x32x2_f32, exact fp32): the full [N,K] output lives in the
-// accumulators of one workgroup (NT x KT tiles of 32x32 over WN x WK waves), the
+// "TN" GEMM whose contraction runs over the huge row dimension.  The full [N,K]
+// output lives in the fp32 MFMA accumulators of one workgroup (NT x KT tiles of
+// 32x32 over WN x WK waves; float32 operands as fp16 hi + lo, bf16 as they are), the
 // workgroup streams its share of rows HBM -> LDS with the async LDS-DMA
 // (global_load_lds, 16 B/lane; a TR-row tile of a row-major matrix is one
 // contiguous chunk, so the LDS image is lane-linear), double buffered, and
-// feeds MFMA operands with conflict-free ds_read_b32 (lane&31 walks a row).
+// feeds MFMA operands with conflict-free LDS reads (lane&31 walks a row).
 // Split-K partials are reduced by a second kernel in a fixed order.
 #include "bf16.h"
 #include "traversal.h"
 #include "wgrad_stream.h"
+#include "f16_scale.h"
 
 #include <cstring>
 #include <type_traits>
@@ -40,73 +41,16 @@ __device__ __forceinline__ void stage_tile(const float* g, float* l, int W, int 
     }
 }
 
-// exact three-way bf16 split of 8 fp32 values (see row_gemm.hip: h + m + l covers all 24 significand
-// bits; the six cross products with i + j <= 4 on v_mfma_f32_32x32x16_bf16 are as accurate as fp32 FMAs)
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ void split8(const float (&x)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    u32x4 hp, mp, lp;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const unsigned a0 = __float_as_uint(x[2 * i]), a1 = __float_as_uint(x[2 * i + 1]);
-        hp[i] = __builtin_amdgcn_perm(a1, a0, 0x07060302u);
-        const float r0 = x[2 * i] - __uint_as_float(a0 & 0xFFFF0000u);
-        const float r1 = x[2 * i + 1] - __uint_as_float(a1 & 0xFFFF0000u);
-        const unsigned b0 = __float_as_uint(r0), b1 = __float_as_uint(r1);
-        mp[i] = __builtin_amdgcn_perm(b1, b0, 0x07060302u);
-        const float s0 = r0 - __uint_as_float(b0 & 0xFFFF0000u);
-        const float s1 = r1 - __uint_as_float(b1 & 0xFFFF0000u);
-        lp[i] = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302u);
-    }
-    h = __builtin_bit_cast(bf16x8, hp);
-    m = __builtin_bit_cast(bf16x8, mp);
-    l = __builtin_bit_cast(bf16x8, lp);
-}
 
-// fp16 hi + lo split of 8 scaled fp32 values: hi = s rounded toward zero to fp16 (11 significant bits), lo = s - hi
-// (exact in fp32) rounded toward zero; hi_a hi_b + hi_a lo_b + lo_a hi_b on v_mfma_f32_32x32x16_f16 leaves a relative
-// error of 2^-22 per product, fp32 accumulate (row_gemm.hip uses the same split for the forward / dgrad GEMMs).
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-// one pair of values: packed hi and lo words
-__device__ __forceinline__ void split2_f16(float v0, float v1, float sc, unsigned& hw, unsigned& lw) {
-    const float s0 = v0 * sc, s1 = v1 * sc;
-    hw = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(s0, s1));      // hi = s rounded toward zero
-    // lo = s - hi, exact in fp32: v_fma_mix_f32 reads the fp16 halves of `hw` directly (hipcc emits cvt + sub)
-    float l0, l1;
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(hw), "v"(s0));
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(hw), "v"(s1));
-    lw = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(l0, l1));
-}
-// 2^(8 - floor(log2 m)) for a finite m > 0: the scale that maps m into [2^8, 2^9).  A column's scale moves again
-// only when a later value is 64-128 times larger than the one that set it (fp16 holds 2^16): on real gradients a
-// tighter window (2^12: 4-8 times) had some column of nearly every 16-row step of a wave moving, and every move
-// costs the wave ~2 steps.  Elements more than 2^11 below their column's running maximum lose relative (not
-// absolute) accuracy: absolute error 2^-25 scaled units = 2^-33 of that maximum.
-__device__ __forceinline__ float scale_for(float m) {
-    const int e = static_cast<int>((__float_as_uint(m) >> 23) & 255u);      // biased exponent (0 for denormals)
-    int be = 127 + 8 - (e - 127);
-    be = be > 253 ? 253 : (be < 1 ? 1 : be);
-    return __uint_as_float(static_cast<unsigned>(be) << 23);
-}
-
-// exact quotient / reciprocal of powers of two by exponent arithmetic (v_rcp_f32 is a 1-ulp approximation)
-__device__ __forceinline__ float pow2_ratio(float num, float den) {      // num <= den
-    const int d = static_cast<int>(__float_as_uint(num) >> 23) - static_cast<int>(__float_as_uint(den) >> 23) + 127;
-    return d < 1 ? 0.f : __uint_as_float(static_cast<unsigned>(d) << 23);
-}
-__device__ __forceinline__ float pow2_inv(float p) {                      // p in [2^-126, 2^126]
-    return __uint_as_float((254u - (__float_as_uint(p) >> 23)) << 23);
-}
-
-// SPLIT 0: fp32 MFMA (v_mfma_f32_32x32x2_f32).  SPLIT 1: operands split into three bf16 planes in registers, 6 MFMAs
-// per 16-row step and tile pair (6/16 of the fp32 matrix time per flop).  SPLIT 2 (default for fp32): fp16 hi + lo,
-// 3 MFMAs per step and tile pair.  fp16 has 5 exponent bits, so every COLUMN of dy and of x carries a running
+// The arithmetic follows from the element type.  bf16: one v_mfma_f32_32x32x16_bf16 per 16-row step and tile pair.
+// float: fp16 hi + lo, 3 MFMAs per step and tile pair.  fp16 has 5 exponent bits, so every COLUMN of dy and of x carries a running
 // power-of-two scale: before a 16-row step is converted, the step's column maxima (8 values per lane + the partner
 // lane) are compared with what the scale can hold; when a column outgrows it, the scale drops so that the new maximum
 // lands in [2^8, 2^9) and the accumulators of that column are multiplied by the (exact) ratio -- a handful of times
 // per launch.  Nothing overflows, the partial sums are un-scaled exactly at the end, and an element far below its
 // column's running maximum keeps an ABSOLUTE error of 2^-25 scaled units, i.e. 2^-33 of that maximum.
-template <typename T, int NT, int KT, int WN, int WK, int TR, bool MASK, int SPLIT = 0, int NBUF = 2>
+template <typename T, int NT, int KT, int WN, int WK, int TR, bool MASK, int NBUF = 2>
 __global__ __launch_bounds__(WN* WK * 64) void wgrad_kernel(const T* __restrict__ dy,
                                                            const T* __restrict__ dymask,
                                                            const T* __restrict__ x,
@@ -117,6 +61,7 @@ __global__ __launch_bounds__(WN* WK * 64) void wgrad_kernel(const T* __restrict_
     constexpr bool BF = std::is_same<T, bf16_t>::value;
     constexpr int EPF = BF ? 2 : 1;             // elements per 4-byte word
     static_assert(NT % WN == 0 && KT % WK == 0, "wave grid must divide the tile grid");
+    static_assert(TR % 16 == 0, "the MFMAs contract 16 rows per step");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     T* lds = reinterpret_cast<T*>(smem_raw);
     // buffers: [NBUF][TR*(N+K)] (dy tile, x tile) or [NBUF][TR*(2N+K)] (dy, x, mask tiles), elements of T.  NBUF > 2: a
@@ -145,7 +90,7 @@ __global__ __launch_bounds__(WN* WK * 64) void wgrad_kernel(const T* __restrict_
     constexpr int H = THREADS >= 2 * N ? 2 : 1;   // row halves for the bias column sums
     static_assert(THREADS >= N, "bias reduction needs one thread per column");
     float bacc = 0.f;   // bias partial: thread t owns column t % N, row part t / N
-    // SPLIT 2: running scales of this lane's column in every dy / x tile of the wave (2^126: nothing seen yet)
+    // float: running scales of this lane's column in every dy / x tile of the wave (2^126: nothing seen yet)
     float scy[TN], scx[TK];
 #pragma unroll
     for (int i = 0; i < TN; ++i) scy[i] = 8.507059e37f;
@@ -196,7 +141,7 @@ __global__ __launch_bounds__(WN* WK * 64) void wgrad_kernel(const T* __restrict_
             bacc += s;
         }
     };
-    if constexpr (SPLIT == 2 && !BF) {
+    if constexpr (!BF) {
         // The accumulators are only touched by MFMAs inside the hot loop: a step whose column maxima outgrow the running
         // scales leaves the loop, the scales move and the accumulators are multiplied OUTSIDE it, and the loop is
         // re-entered at the same 16-row step (hipcc otherwise copies all 96 accumulator registers around the branch
@@ -267,7 +212,6 @@ __global__ __launch_bounds__(WN* WK * 64) void wgrad_kernel(const T* __restrict_
                 // alternate INSIDE a wave: operand tiles are split in the order y0, x0, x1.., y1.., and the split of
                 // each one is interleaved (scheduling fences) with the MFMAs of the tile pairs the previous split
                 // completed; the pairs of the last split run at the end.
-                typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
                 u32x4 yh[TN], yl[TN], xh[TK], xl[TK];
                 auto split_pair = [&](int job, int pr) {      // job: 0 = y0, 1..TK = x(job-1), TK+1.. = y(job-TK)
                     if (job == 0 || job > TK) {
@@ -356,97 +300,46 @@ __global__ __launch_bounds__(WN* WK * 64) void wgrad_kernel(const T* __restrict_
         const T* ldy = lds + buf * BUF;
         const T* lx = ldy + TR * N;
         const int half = lane >> 5, col = lane & 31;
-        if constexpr (BF) {
-            // bf16 operands: the fragment of lane (column, half) is the 8 consecutive ROWS 16 s + 8 half + j of
-            // its column -- eight 2-byte LDS reads (32 lanes cover 64 contiguous bytes: conflict free), one MFMA
-            // per tile pair and 16-row step
-            const unsigned short* uy = reinterpret_cast<const unsigned short*>(ldy);
-            const unsigned short* ux = reinterpret_cast<const unsigned short*>(lx);
+        // bf16 operands: the fragment of lane (column, half) is the 8 consecutive ROWS 16 s + 8 half + j of
+        // its column -- eight 2-byte LDS reads (32 lanes cover 64 contiguous bytes: conflict free), one MFMA
+        // per tile pair and 16-row step
+        const unsigned short* uy = reinterpret_cast<const unsigned short*>(ldy);
+        const unsigned short* ux = reinterpret_cast<const unsigned short*>(lx);
 #pragma unroll
-            for (int s16 = 0; s16 < TR / 16; ++s16) {
-                bf16x8 af[TN], bfg[TK];
-#pragma unroll
-                for (int i = 0; i < TN; ++i) {
-                    u32x4_t pk;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int o0 = (16 * s16 + 8 * half + 2 * j) * N + (wn * TN + i) * 32 + col;
-                        unsigned lo = uy[o0], hi = uy[o0 + N];
-                        if (MASK) {
-                            const unsigned short m0 = ux[TR * K + o0], m1 = ux[TR * K + o0 + N];
-                            // keep where the saved activation is > 0 (positive, non-zero bf16)
-                            lo = (m0 != 0 && !(m0 & 0x8000u)) ? lo : 0u;
-                            hi = (m1 != 0 && !(m1 & 0x8000u)) ? hi : 0u;
-                        }
-                        pk[j] = lo | (hi << 16);
-                    }
-                    af[i] = __builtin_bit_cast(bf16x8, pk);
-                }
-#pragma unroll
-                for (int j2 = 0; j2 < TK; ++j2) {
-                    u32x4_t pk;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int o0 = (16 * s16 + 8 * half + 2 * j) * K + (wk * TK + j2) * 32 + col;
-                        pk[j] = static_cast<unsigned>(ux[o0]) | (static_cast<unsigned>(ux[o0 + K]) << 16);
-                    }
-                    bfg[j2] = __builtin_bit_cast(bf16x8, pk);
-                }
-#pragma unroll
-                for (int i = 0; i < TN; ++i)
-#pragma unroll
-                    for (int j2 = 0; j2 < TK; ++j2)
-                        acc[i][j2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfg[j2], acc[i][j2], 0, 0, 0);
-            }
-        } else
-        if constexpr (SPLIT == 1) {
-#pragma unroll
-            for (int s16 = 0; s16 < TR / 16; ++s16) {
-                bf16x8 af[TN][3], bfg[TK][3];
-#pragma unroll
-                for (int i = 0; i < TN; ++i) {
-                    float v[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int o = (16 * s16 + 8 * half + j) * N + (wn * TN + i) * 32 + col;
-                        v[j] = ldy[o];
-                        if (MASK) v[j] = lx[TR * K + o] > 0.f ? v[j] : 0.f;
-                    }
-                    split8(v, af[i][0], af[i][1], af[i][2]);
-                }
-#pragma unroll
-                for (int j2 = 0; j2 < TK; ++j2) {
-                    float v[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] = lx[(16 * s16 + 8 * half + j) * K + (wk * TK + j2) * 32 + col];
-                    split8(v, bfg[j2][0], bfg[j2][1], bfg[j2][2]);
-                }
-                constexpr int TA[6] = {2, 1, 0, 1, 0, 0}, TB[6] = {0, 1, 2, 0, 1, 0};   // smallest terms first
-#pragma unroll
-                for (int t = 0; t < 6; ++t)
-#pragma unroll
-                    for (int i = 0; i < TN; ++i)
-#pragma unroll
-                        for (int j2 = 0; j2 < TK; ++j2)
-                            acc[i][j2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][TA[t]], bfg[j2][TB[t]], acc[i][j2], 0, 0, 0);
-            }
-        } else
-#pragma unroll
-        for (int ks = 0; ks < TR / 2; ++ks) {
-            float a[TN], b[TK];
+        for (int s16 = 0; s16 < TR / 16; ++s16) {
+            bf16x8 af[TN], bfg[TK];
 #pragma unroll
             for (int i = 0; i < TN; ++i) {
-                const int o = (2 * ks + half) * N + (wn * TN + i) * 32 + col;
-                a[i] = ldy[o];
-                if (MASK) a[i] = lx[TR * K + o] > 0.f ? a[i] : 0.f;
+                u32x4_t pk;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int o0 = (16 * s16 + 8 * half + 2 * j) * N + (wn * TN + i) * 32 + col;
+                    unsigned lo = uy[o0], hi = uy[o0 + N];
+                    if (MASK) {
+                        const unsigned short m0 = ux[TR * K + o0], m1 = ux[TR * K + o0 + N];
+                        // keep where the saved activation is > 0 (positive, non-zero bf16)
+                        lo = (m0 != 0 && !(m0 & 0x8000u)) ? lo : 0u;
+                        hi = (m1 != 0 && !(m1 & 0x8000u)) ? hi : 0u;
+                    }
+                    pk[j] = lo | (hi << 16);
+                }
+                af[i] = __builtin_bit_cast(bf16x8, pk);
             }
 #pragma unroll
-            for (int j = 0; j < TK; ++j) b[j] = lx[(2 * ks + half) * K + (wk * TK + j) * 32 + col];
+            for (int j2 = 0; j2 < TK; ++j2) {
+                u32x4_t pk;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int o0 = (16 * s16 + 8 * half + 2 * j) * K + (wk * TK + j2) * 32 + col;
+                    pk[j] = static_cast<unsigned>(ux[o0]) | (static_cast<unsigned>(ux[o0 + K]) << 16);
+                }
+                bfg[j2] = __builtin_bit_cast(bf16x8, pk);
+            }
 #pragma unroll
             for (int i = 0; i < TN; ++i)
 #pragma unroll
-                for (int j = 0; j < TK; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
+                for (int j2 = 0; j2 < TK; ++j2)
+                    acc[i][j2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfg[j2], acc[i][j2], 0, 0, 0);
         }
         if (part_b) bias_tile(buf);
     }
@@ -461,7 +354,7 @@ __global__ __launch_bounds__(WN* WK * 64) void wgrad_kernel(const T* __restrict_
             for (int reg = 0; reg < 16; ++reg) {
                 const int row = (reg & 3) + 8 * (reg >> 2) + 4 * half;
                 float val = acc[i][j][reg];
-                if constexpr (SPLIT == 2 && !BF) {      // un-scale: two exact multiplications (each factor within fp32 range)
+                if constexpr (!BF) {      // un-scale: two exact multiplications (each factor within fp32 range)
                     const float iy = pow2_inv(scy[i]);
                     val = val * __int_as_float(__builtin_amdgcn_ds_bpermute(row * 4, __float_as_int(iy)));
                     val = val * pow2_inv(scx[j]);
@@ -640,11 +533,10 @@ bool wgrad_plan(int N, int K, WgradPlan* p) {
     struct Row {
         int nt, kt, wn, wk, tr;
     };
-    constexpr bool big = false;
     static const Row table[] = {
-        {4, 4, 2, 2, big ? 64 : 32},   // 128 x 128   (q,k,v,e,out_e,out_n)
-        {12, 4, 4, 2, big ? 32 : 16},  // 384 x 128   (fc1: dW[3C, C])
-        {4, 12, 2, 4, big ? 32 : 16},  // 128 x 384   (fc2: dW[C, 3C])
+        {4, 4, 2, 2, 32},   // 128 x 128   (q,k,v,e,out_e,out_n)
+        {12, 4, 4, 2, 16},  // 384 x 128   (fc1: dW[3C, C])
+        {4, 12, 2, 4, 16},  // 128 x 384   (fc2: dW[C, 3C])
         {4, 2, 2, 2, 32},   // 128 x 64    (embedding layer 2: Linear(64, C))
         {2, 2, 2, 2, 32},   // 64 x 64
         {1, 1, 1, 1, 32},   // 32 x 32     (tiny test models)
@@ -810,59 +702,48 @@ extern "C" int dg_linear_wgrad(const void* dy_, const void* dy_mask_, const void
     if (workspace_bytes < dg_linear_wgrad_workspace_bytes(R, N, K))
         return fail(DG_E_WORKSPACE, "dg_linear_wgrad: workspace too small");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    // fp32 operands: fp16 hi + lo with running column scales (the bf16x6 split and the plain fp32 MFMA of rounds 1 - 2 are no
-    // longer selectable); the three encoder shapes run on the producer / consumer kernel (wgrad_stream.hip), every element
-    // converted once per workgroup, the other shapes on the symmetric kernel below
-    constexpr int split = 2;
-    constexpr bool stream_kernel = true;
-    const bool use_stream = !bf && split == 2 && stream_kernel && !dy_mask_ && wgrad_stream_supported(N, K);
+    // fp32 operands: fp16 hi + lo with running column scales; the three encoder shapes run on the producer / consumer
+    // kernel (wgrad_stream.hip), every element converted once per workgroup, the other shapes (and dy_mask) on the
+    // symmetric kernel above
+    const bool use_stream = !bf && !dy_mask_ && wgrad_stream_supported(N, K);
     if (hfmt && !use_stream)
         return fail(DG_E_ARG, "dg_linear_wgrad: DG_DTYPE_F32_H16 / _H24 needs one of the producer / consumer weight-gradient shapes");
     int tpb;
     const bool may_wait = g_batch_on && g_batch_n < 8;      // (a launch may only wait for a carrier when its reduce is deferred too)
     const int S = use_stream ? wgrad_stream_blocks(R, N, K, may_wait)
-                             : wgrad_blocks(R, p, &tpb, !bf && split != 0 && p.nt + p.kt == 16 && p.tr % 16 == 0);
+                             : wgrad_blocks(R, p, &tpb, !bf && p.nt + p.kt == 16);
     float* part_w = static_cast<float*>(workspace);
     float* part_b = db ? part_w + static_cast<size_t>(S) * N * K : nullptr;
-    const bool big_tiles = (p.nt == 4 && p.kt == 4) ? p.tr == 64 : p.tr == 32;
     ProfScope prof(wgrad_prof_key(R, N, K), stream);
     note_forward(R);
     if (use_stream) {
         if (int st = launch_wgrad_stream(dy_, x_, part_w, part_b, R, N, K, S, stream, nullptr, nullptr, may_wait, hscale, hfmt))
             return st;
     } else {
-#define LAUNCH_X(T, NT_, KT_, WN_, WK_, TR_, M_, X_)                                                              \
+#define LAUNCH_X(T, NT_, KT_, WN_, WK_, TR_, M_)                                                                   \
     {                                                                                                            \
         constexpr int tile_bytes = TR_ * ((M_ ? 2 : 1) * NT_ + KT_) * 32 * static_cast<int>(sizeof(T));           \
         /* fp32 384-wide shapes: one block per CU (registers), so a deeper ring instead of a second block */     \
-        constexpr int nbuf = (sizeof(T) == 4 && X_ != 0 && NT_ + KT_ == 16) ? (4 * tile_bytes <= 131072 ? 4 : (3 * tile_bytes <= 131072 ? 3 : 2)) : 2; \
+        constexpr int nbuf = (sizeof(T) == 4 && NT_ + KT_ == 16) ? (4 * tile_bytes <= 131072 ? 4 : (3 * tile_bytes <= 131072 ? 3 : 2)) : 2; \
         constexpr int lds_bytes = nbuf * tile_bytes;                                                              \
-        DG_OPT_IN_LDS((&wgrad_kernel<T, NT_, KT_, WN_, WK_, TR_, M_, X_, nbuf>), lds_bytes);                      \
-        hipLaunchKernelGGL((wgrad_kernel<T, NT_, KT_, WN_, WK_, TR_, M_, X_, nbuf>), dim3(S), dim3(WN_* WK_ * 64), \
+        DG_OPT_IN_LDS((&wgrad_kernel<T, NT_, KT_, WN_, WK_, TR_, M_, nbuf>), lds_bytes);                          \
+        hipLaunchKernelGGL((wgrad_kernel<T, NT_, KT_, WN_, WK_, TR_, M_, nbuf>), dim3(S), dim3(WN_* WK_ * 64),     \
                            lds_bytes, stream, static_cast<const T*>(dy_), static_cast<const T*>(dy_mask_),       \
                            static_cast<const T*>(x_), part_w, part_b, R, tpb);                                   \
     }
-#define LAUNCH_M(NT_, KT_, WN_, WK_, TR_, M_)                                            \
-    {                                                                                   \
-        if (bf) LAUNCH_X(bf16_t, NT_, KT_, WN_, WK_, TR_, M_, 0)                         \
-        else if (split == 2 && (TR_) % 16 == 0) LAUNCH_X(float, NT_, KT_, WN_, WK_, TR_, M_, 2) \
-        else if (split == 1 && (TR_) % 16 == 0) LAUNCH_X(float, NT_, KT_, WN_, WK_, TR_, M_, 1) \
-        else LAUNCH_X(float, NT_, KT_, WN_, WK_, TR_, M_, 0)                             \
+#define LAUNCH_M(NT_, KT_, WN_, WK_, TR_, M_)                       \
+    {                                                              \
+        if (bf) LAUNCH_X(bf16_t, NT_, KT_, WN_, WK_, TR_, M_)       \
+        else LAUNCH_X(float, NT_, KT_, WN_, WK_, TR_, M_)           \
     }
 #define LAUNCH(NT_, KT_, WN_, WK_, TR_)                                   \
     if (p.nt == NT_ && p.kt == KT_) {                                     \
         if (dy_mask_) LAUNCH_M(NT_, KT_, WN_, WK_, TR_, true)             \
         else LAUNCH_M(NT_, KT_, WN_, WK_, TR_, false)                     \
     }
-    if (big_tiles) {
-        LAUNCH(4, 4, 2, 2, 64)
-        LAUNCH(12, 4, 4, 2, 32)
-        LAUNCH(4, 12, 2, 4, 32)
-    } else {
-        LAUNCH(4, 4, 2, 2, 32)
-        LAUNCH(12, 4, 4, 2, 16)
-        LAUNCH(4, 12, 2, 4, 16)
-    }
+    LAUNCH(4, 4, 2, 2, 32)
+    LAUNCH(12, 4, 4, 2, 16)
+    LAUNCH(4, 12, 2, 4, 16)
     LAUNCH(4, 2, 2, 2, 32)
     LAUNCH(2, 2, 2, 2, 32)
     LAUNCH(1, 1, 1, 1, 32)

@@ -1,27 +1,20 @@
-// fp32-MFMA "row GEMM" for the per-edge / per-node dense layers of DrugGEN's
-// encoder (reference src/model/layers.py: MHA projections :111-116,127,135 and
-// MLP.fc1/fc2 :50-53), with the elementwise neighbours of those GEMMs fused in:
+// "Row GEMM" for the per-edge / per-node dense layers of DrugGEN's encoder (reference src/model/layers.py: MHA
+// projections :111-116,127,135 and MLP.fc1/fc2 :50-53), float32 activations, with the elementwise neighbours of
+// those GEMMs fused in:
 //
 //     Y[R,N] = epilogue( prologue(A)[R,K] . B )        R = B*N*N rows (518 400 at configs[1])
 //
 //   forward   B[k][n] = W[n][k]    (y = x W^T + b)          -> pack mode 0
 //   dgrad     B[k][n] = W[k][n]    (dx = dy W)              -> pack mode 1
-//   prologue: A, or A * (mask > 0)            (ReLU backward folded into the operand load)
-//   epilogue: + bias, ReLU, * (mask > 0), + residual, LayerNorm(gamma, beta) -> y (+ mean, rstd)
+//   epilogue: + bias, ReLU, + residual, LayerNorm(gamma, beta) -> y (+ mean, rstd), or a LayerNorm backward
 //
-// MI355X mapping
-//   * v_mfma_f32_32x32x2_f32 (exact fp32).  A workgroup (4 waves) owns a 64-row tile; wave w owns
-//     the 32-column slab w of a 128-column chunk for both 32-row halves (2 accumulators).
-//   * The weight operand never touches LDS: a tiny pack kernel re-orders W once per weight
-//     version into MFMA *fragment order*, so each wave streams its B fragments for a 128x128
-//     weight block as 16 perfectly coalesced float4 loads straight into 64 VGPRs (L2-resident).
-//     The contraction index is permuted (lanes 0-31 take k = 4q+j, lanes 32-63 take k = 64+4q+j)
-//     so that both operands are read 16 bytes at a time.
-//   * The activation tile goes HBM -> VGPR (16 B/lane, coalesced rows) -> LDS with a 528-byte
-//     row pitch: ds_read_b128 of the A fragments is bank-conflict free.
-//   * LayerNorm epilogue: the 64x128 result tile is exchanged through LDS so that each wave
-//     normalises whole rows (32 lanes x float4, 5-step butterflies) and stores full 512 B rows.
+// This file: the host entry points, the weight pack (fp16 hi + lo planes in MFMA fragment order, never through LDS), the
+// 128 -> 128 kernels (row_gemm_h3_kernel, also the three-output 128 -> 384 form of the q / k / v launch) and the 384 -> 128
+// kernel over three separate [R,128] operands (row_gemm_h3_k384_kernel).  The edge-level 128 -> 384 and 384 -> 128 GEMMs
+// are row_gemm_n384.hip and row_gemm_k384.hip.  The fp32-MFMA and bf16 x 6 kernels of rounds 1 - 2 are gone.
 #include "common.h"
+#include "f16_scale.h"
+#include "lane_reduce.h"
 #include "row_gemm_n384.h"
 #include "row_gemm_k384.h"
 #include "traversal.h"
@@ -43,33 +36,6 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kTR = 64;          // rows per workgroup tile
-constexpr int kPitch = 132;      // LDS row pitch in floats for a 128-wide tile (528 B)
-
-// ---------------------------------------------------------------- weight packing --
-// P[((t*KC + c)*16 + q)*64 + lane] (float4), t = 32-column tile of the output, c = 128-wide
-// chunk of the contraction, lane = (n = lane & 31, h = lane >> 5):
-//   mode 0 (forward): { W[32t+n][128c + 64h + 4q + j] }_j           W: [Nout, Kin]
-//   mode 1 (dgrad)  : { W[128c + 64h + 4q + j][32t+n] }_j           W: [Kcontract, Nout']
-__global__ void pack_weight_kernel(const float* __restrict__ w, float* __restrict__ p, int rows, int cols, int mode,
-                                   int n_tiles, int k_chunks) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;   // one float4 each
-    const int total = n_tiles * k_chunks * 16 * 64;
-    if (idx >= total) return;
-    const int lane = idx & 63, q = (idx >> 6) & 15;
-    const int c = (idx >> 10) % k_chunks, t = (idx >> 10) / k_chunks;
-    const int n = 32 * t + (lane & 31);
-    const int k0 = 128 * c + 64 * (lane >> 5) + 4 * q;
-    float v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int k = k0 + j;
-        if (mode == 0)
-            v[j] = (n < rows && k < cols) ? w[static_cast<size_t>(n) * cols + k] : 0.f;
-        else
-            v[j] = (k < rows && n < cols) ? w[static_cast<size_t>(k) * cols + n] : 0.f;
-    }
-    st4(p + static_cast<size_t>(idx) * 4, make_float4(v[0], v[1], v[2], v[3]));
-}
 
 struct Epilogue {
     const float* bias;      // [N] or null
@@ -105,370 +71,16 @@ struct Epilogue {
     int reverse = 0;      // 128 -> 128 kernels without LayerNorm-backward stages: tiles in descending order (traversal.h)
 };
 
-// Sum over the 32 lanes of a half-wave, result in every lane.  DPP adds inside each 16-lane row
-// (quad xor 1, quad xor 2, half-row mirror, row mirror), then the two row totals of the half-wave are
-// read as scalars: no LDS-crossbar round trips (a __shfl_xor butterfly is five dependent ds_bpermute).
-template <int CTRL>
-__device__ __forceinline__ float dpp_sum_step(float x) {
-    const int moved = __builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, true);
-    return x + __int_as_float(moved);
-}
-__device__ __forceinline__ float half_sum(float x) {
-    x = dpp_sum_step<0xB1>(x);    // quad_perm [1,0,3,2]
-    x = dpp_sum_step<0x4E>(x);    // quad_perm [2,3,0,1]
-    x = dpp_sum_step<0x141>(x);   // row_half_mirror
-    x = dpp_sum_step<0x140>(x);   // row_mirror: every lane holds its 16-lane row total
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 0));
-    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 32));
-    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 48));
-    return (threadIdx.x & 32) ? r2 + r3 : r0 + r1;
-}
+// sum over the 32 lanes of a half-wave, result in every lane (lane_reduce.h)
+__device__ __forceinline__ float half_sum(float x) { return half_wave_total_readlane(x, threadIdx.x & 32); }
 
-// Persistent row-GEMM workgroup.
-//   KC  = K/128 contraction chunks (B fragments for all of them stay in VGPRs for the whole kernel)
-//   NG  = N/128 output chunks, one 4-wave group each (all groups share the A tile)
-//   MG  = row groups of waves: the TR-row tile is split into MG slabs of MT = TR/32/MG 32-row blocks
-//   TR  = rows per tile
-//   EXCH = epilogue through an LDS exchange tile (row-wise float4 residual loads / stores,
-//          optional LayerNorm; NG == MG == 1); otherwise direct stores from the accumulator layout,
-//          software-pipelined: the stores of tile t-1 are issued inside the MFMA phase of tile t.
-// A tiles arrive by LDS-DMA into a double buffer; the LDS image is the global image with the
-// 16-byte chunk index XOR-ed by (row & 15) inside every 512-byte segment (applied on the per-lane
-// SOURCE address, the DMA destination is lane-linear), which makes the ds_read_b128 fragment
-// reads bank-conflict free without padding.
-template <int KC, int NG, int MG, int TR, bool EXCH, bool PIPE, int MINW, bool XPIPE = false>
-__global__ __launch_bounds__(NG * MG * 256, MINW) void row_gemm_kernel(const float* __restrict__ a,
-                                                                const float* __restrict__ packed,
-                                                                float* __restrict__ y, int64_t R, Epilogue ep) {
-    constexpr int K = KC * 128, N = NG * 128, MT = TR / 32 / MG, WAVES = NG * MG * 4;
-    constexpr int SLOTS = TR * K / 4;            // 16-byte slots per tile
-    constexpr int STEPS = KC * 16;               // MFMA steps (4 MFMAs per 32-row block each)
-    static_assert(!EXCH || (NG == 1 && MG == 1), "exchange epilogue needs the whole tile in one group");
-    static_assert(TR % (32 * MG) == 0, "tile rows must split evenly over the row groups");
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float* lds = reinterpret_cast<float*>(smem_raw);   // [2][TR*K] (+ [TR][128] exchange tile when XPIPE)
-    float* xtile = lds + 2 * TR * K;
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wq = w & 3, g = (w >> 2) % NG, mg = (w >> 2) / NG;
-    const int half = lane >> 5, col = lane & 31;
-    const int64_t tiles = (R + TR - 1) / TR;
-    const int n = 128 * g + 32 * wq + col;
-    const int row_base = 32 * MT * mg;           // first tile row of this wave's slab
-
-    float4 bf[KC][16];
-#pragma unroll
-    for (int kc = 0; kc < KC; ++kc)
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-            bf[kc][q] = ld4(packed + (static_cast<size_t>((4 * g + wq) * KC + kc) * 16 + q) * 256 + lane * 4);
-    const float bias = ep.bias ? ep.bias[n] : 0.f;
-
-    auto dma_tile = [&](int64_t tile, int buf) {
-        const int64_t r0 = tile * TR;
-        const unsigned dst = lds_byte_address(lds + buf * (TR * K));
-        for (int ii = w; ii < SLOTS / 64; ii += WAVES) {
-            const int L = ii * 64 + lane;
-            const int row = L / (K / 4), cs = L % (K / 4);
-            const int src = (cs & ~31) | ((cs & 31) ^ (row & 15));
-            if (r0 + row < R) dma16_async(a + (r0 + row) * K + src * 4, dst + ii * 1024);
-        }
-    };
-    // direct epilogue of one accumulator register (tile rows r0.., this lane's column n)
-    auto store_reg = [&](const f32x16 (&acc)[MT], int64_t r0, unsigned bits, int m, int reg, unsigned& newbits) {
-        const int64_t row = r0 + row_base + 32 * m + (reg & 3) + 8 * (reg >> 2) + 4 * half;
-        float v = acc[m][reg] + bias;
-        if (ep.relu) {
-            newbits |= (v > 0.f ? 1u : 0u) << (16 * m + reg);
-            v = fmaxf(v, 0.f);
-        }
-        if (ep.mask_bits) v = (bits >> (16 * m + reg)) & 1u ? v : 0.f;
-        if (row < R) y[row * N + n] = v;
-    };
-
-    // exchange-epilogue helpers (EXCH): the wave's accumulators go to a [TR][128] LDS tile, then every
-    // half-wave finalises whole rows (residual add, optional LayerNorm, 512 B stores)
-    auto exch_write = [&](float* ex, const f32x16 (&acc)[MT], int m, int reg) {
-        const int rr = 32 * m + (reg & 3) + 8 * (reg >> 2) + 4 * half;
-        float v = acc[m][reg] + bias;
-        if (ep.relu) v = fmaxf(v, 0.f);
-        ex[rr * 128 + 32 * wq + col] = v;
-    };
-    auto exch_row = [&](const float* ex, int64_t r0, int it, float4 res) {
-        const int rr = wq * (TR / 4) + it * 2 + half;
-        const int64_t row = r0 + rr;
-        const bool ok = row < R;
-        float4 v = ld4(ex + rr * 128 + col * 4);
-        if (ep.residual) v += res;
-        if (ep.gamma == nullptr) {
-            if (ok) st4(y + row * N + col * 4, v);
-            return;
-        }
-        if (ep.pre && ok) st4(ep.pre + row * N + col * 4, v);
-        const float mu = half_sum((v.x + v.y) + (v.z + v.w)) * (1.0f / 128.0f);
-        const float4 d = v - f4(mu);
-        const float var = half_sum((d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w)) * (1.0f / 128.0f);
-        const float rs = rsqrtf(var + ep.eps);
-        if (ok) {
-            st4(y + row * N + col * 4, fma4(rs * d, ld4(ep.gamma + col * 4), ld4(ep.beta + col * 4)));
-            if (col == 0) {
-                ep.mean[row] = mu;
-                ep.rstd[row] = rs;
-            }
-        }
-    };
-    auto load_res = [&](int64_t r0, int it) {
-        int64_t row = r0 + wq * (TR / 4) + it * 2 + half;
-        if (row >= R) row = R - 1;
-        return ep.residual ? ld4(ep.residual + row * N + col * 4) : f4(0.f);
-    };
-    float4 resP[TR / 8], resN[TR / 8];   // XPIPE: residual rows of the previous / current tile
-
-    wait_all_vmem_visible();   // B fragments and bias are in registers (and the compiler knows it)
-    int64_t tix = blockIdx.x;
-    if (tix < tiles) dma_tile(tix, 0);
-    wait_all_vmem();
-    __syncthreads();
-    int buf = 0;
-    f32x16 accP[MT];            // accumulators of the previous tile, stored during this tile's MFMA phase
-    int64_t r0P = 0, tixP = -1;
-    for (; tix < tiles; tix += gridDim.x, buf ^= 1) {
-        const int64_t r0 = tix * TR;
-        unsigned bitsP = 0, newbits = 0;
-        if (!EXCH && PIPE && tixP >= 0 && ep.mask_bits) {
-            bitsP = ep.mask_bits[(tixP * WAVES + w) * 64 + lane];
-            wait_all_vmem_visible();      // issued before this tile's DMA: does not wait for it
-        }
-        if (EXCH && XPIPE) {   // issued before the DMA: the end-of-phase vmcnt(0) covers them
-#pragma unroll
-            for (int it = 0; it < TR / 8; ++it) resN[it] = load_res(r0, it);
-        }
-        if (tix + gridDim.x < tiles) dma_tile(tix + gridDim.x, buf ^ 1);
-        const float* at = lds + buf * (TR * K);
-        f32x16 acc[MT];
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[m][i] = 0.f;
-        // A fragments are read one step ahead of the MFMAs that consume them
-        float4 nxt[MT];
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-            nxt[m] = ld4(at + (row_base + 32 * m + col) * K + (((16 * half) ^ (col & 15)) << 2));
-#pragma unroll
-        for (int st = 0; st < STEPS; ++st) {
-            const int kc = st / 16, q = st % 16;
-            float4 af[MT];
-#pragma unroll
-            for (int m = 0; m < MT; ++m) af[m] = nxt[m];
-            if (st + 1 < STEPS) {
-                const int kc2 = (st + 1) / 16, q2 = (st + 1) % 16;
-#pragma unroll
-                for (int m = 0; m < MT; ++m)
-                    nxt[m] = ld4(at + (row_base + 32 * m + col) * K + kc2 * 128 + (((16 * half + q2) ^ (col & 15)) << 2));
-            }
-#pragma unroll
-            for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[m].x, bf[kc][q].x, acc[m], 0, 0, 0);
-#pragma unroll
-            for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[m].y, bf[kc][q].y, acc[m], 0, 0, 0);
-#pragma unroll
-            for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[m].z, bf[kc][q].z, acc[m], 0, 0, 0);
-#pragma unroll
-            for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[m].w, bf[kc][q].w, acc[m], 0, 0, 0);
-            if (EXCH && XPIPE && tixP >= 0) {
-                // previous tile's exchange epilogue rides inside this tile's MFMA phase:
-                // steps 0..3 scatter the old accumulators into the exchange tile, a barrier, then one
-                // row pair per step is finalised; everything is issued in the first half of the phase
-                constexpr int WR = 16 * MT / 4;
-                if (st < 4) {
-#pragma unroll
-                    for (int i = 0; i < WR; ++i) exch_write(xtile, accP, (st * WR + i) / 16, (st * WR + i) % 16);
-                    if (st == 3) __syncthreads();
-                } else if (st - 4 < TR / 8) {
-                    exch_row(xtile, r0P, st - 4, resP[st - 4]);
-                }
-            }
-            if (!EXCH && PIPE) {
-                // previous tile's stores ride in the shadow of this tile's MFMAs (first steps only, so
-                // they have drained by the time the DMA wait below needs vmcnt == 0)
-                constexpr int PER = (16 * MT + 7) / 8;          // registers stored per step, 8 steps
-                if (st < 8 && tixP >= 0) {
-#pragma unroll
-                    for (int i = 0; i < PER; ++i) {
-                        const int r = st * PER + i;
-                        if (r < 16 * MT) store_reg(accP, r0P, bitsP, r / 16, r % 16, newbits);
-                    }
-                }
-            }
-        }
-        // the next tile's DMA had the whole MFMA phase to land; the stores above were issued early
-        wait_all_vmem();
-        if (!EXCH && PIPE) {
-            if (ep.relu_bits && tixP >= 0) ep.relu_bits[(tixP * WAVES + w) * 64 + lane] = newbits;
-#pragma unroll
-            for (int m = 0; m < MT; ++m) accP[m] = acc[m];
-            r0P = r0;
-            tixP = tix;
-            __syncthreads();   // every wave: DMA(t+1) landed, tile t fully read
-        } else if (!EXCH) {
-            // many waves per SIMD: the other waves' MFMA phases hide this epilogue
-            const unsigned bits = ep.mask_bits ? ep.mask_bits[(tix * WAVES + w) * 64 + lane] : 0u;
-            unsigned nb = 0;
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) store_reg(acc, r0, bits, m, reg, nb);
-            if (ep.relu_bits) ep.relu_bits[(tix * WAVES + w) * 64 + lane] = nb;
-            __syncthreads();
-        } else if (XPIPE) {
-#pragma unroll
-            for (int m = 0; m < MT; ++m) accP[m] = acc[m];
-#pragma unroll
-            for (int it = 0; it < TR / 8; ++it) resP[it] = resN[it];
-            r0P = r0;
-            tixP = tix;
-            __syncthreads();   // DMA(t+1) landed everywhere, tile t read, exchange tile consumed
-        } else {
-            float* ex = lds + buf * (TR * K);   // consumed A buffer becomes the [TR][128] exchange tile
-            __syncthreads();                    // all waves finished their fragment reads
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) {
-                    const int rr = 32 * m + (reg & 3) + 8 * (reg >> 2) + 4 * half;
-                    float v = acc[m][reg] + bias;
-                    if (ep.relu) v = fmaxf(v, 0.f);
-                    ex[rr * 128 + 32 * wq + col] = v;
-                }
-            __syncthreads();
-            float4 res[TR / 8];
-            if (ep.residual) {
-#pragma unroll
-                for (int it = 0; it < TR / 8; ++it) {
-                    int64_t row = r0 + wq * (TR / 4) + it * 2 + half;
-                    if (row >= R) row = R - 1;
-                    res[it] = ld4(ep.residual + row * N + col * 4);
-                }
-            }
-#pragma unroll
-            for (int it = 0; it < TR / 8; ++it) {
-                const int rr = wq * (TR / 4) + it * 2 + half;
-                const int64_t row = r0 + rr;
-                const bool ok = row < R;
-                float4 v = ld4(ex + rr * 128 + col * 4);
-                if (ep.residual) v += res[it];
-                if (ep.gamma == nullptr) {
-                    if (ok) st4(y + row * N + col * 4, v);
-                    continue;
-                }
-                if (ep.pre && ok) st4(ep.pre + row * N + col * 4, v);
-                const float mu = half_sum((v.x + v.y) + (v.z + v.w)) * (1.0f / 128.0f);
-                const float4 d = v - f4(mu);
-                const float var = half_sum((d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w)) * (1.0f / 128.0f);
-                const float rs = rsqrtf(var + ep.eps);
-                if (ok) {
-                    st4(y + row * N + col * 4, fma4(rs * d, ld4(ep.gamma + col * 4), ld4(ep.beta + col * 4)));
-                    if (col == 0) {
-                        ep.mean[row] = mu;
-                        ep.rstd[row] = rs;
-                    }
-                }
-            }
-            __syncthreads();   // exchange tile consumed before the next DMA overwrites it
-        }
-    }
-    if (EXCH && XPIPE && tixP >= 0) {   // drain: exchange epilogue of the last tile (block-uniform)
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) exch_write(xtile, accP, m, reg);
-        __syncthreads();
-#pragma unroll
-        for (int it = 0; it < TR / 8; ++it) exch_row(xtile, r0P, it, resP[it]);
-    }
-    if (!EXCH && PIPE && tixP >= 0) {   // drain: epilogue of the last tile
-        unsigned bitsP = ep.mask_bits ? ep.mask_bits[(tixP * WAVES + w) * 64 + lane] : 0u, newbits = 0;
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) store_reg(accP, r0P, bitsP, m, reg, newbits);
-        if (ep.relu_bits) ep.relu_bits[(tixP * WAVES + w) * 64 + lane] = newbits;
-    }
-}
-
-
-// =====================================================================================================
-// bf16x6 row GEMM: fp32 operands split three ways into bf16 (a = a1 + a2 + a3, 8 mantissa bits each),
-// the six cross products with i + j <= 4 run on v_mfma_f32_32x32x16_bf16 with fp32 accumulation.
-// The dropped terms are <= 2^-23 |a b|, and every kept product is exact, so the result is as accurate
-// as an fp32 FMA chain (measured against fp64: rms 1.9e-8 / max 1.0e-7 of sum|a b| at K = 128, versus
-// 2.4e-8 / 1.6e-7 for v_mfma_f32_32x32x2_f32 -- scripts/ubench/mfma_bf16_layout.hip and
-// tests/test_hip_kernels.py) while the MFMA time drops to 6/16 of the fp32 pipe's: the GEMMs stop being
-// MFMA-bound and run at the HBM roof of their activation streams.
-//
-//   * packed weights: for output slab t (32 columns), k-step ks (16 k) and plane p the B fragment of
-//     lane (n = lane & 31, kg = lane >> 5) is the 8 bf16 { B[ks*16 + 8 kg + j][32 t + n] }_j.
-//   * workgroup = 4 waves, wave w = slab w of a 128-column group (blockIdx.y), 64-row tiles, 2 workgroups
-//     per CU.  A tile chunks (64 x 128 fp32) go HBM -> registers (prefetched one chunk ahead) -> split ->
-//     three bf16 planes in LDS (272-byte row pitch: conflict-free ds_read_b128 fragments).
-//   * K = 384 is three chunks accumulated into the same accumulators; the B fragments of a chunk (96
-//     VGPRs) are re-read from L2 while the next chunk is being split.
-//   * N = 384 is three column groups (gridDim.y): the groups of one tile sequence share an XCD
-//     (gridDim.x is a multiple of 8), so two of the three reads of an A tile hit L2.
-// LDS-DMA with a scalar chunk base and a per-lane 32-bit byte offset (3 instructions per 1 KiB piece)
-__device__ __forceinline__ void dma16_saddr(const float* base, unsigned lane_off, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                 :
-                 : "v"(lane_off), "s"(base), "s"(lds_addr)
-                 : "memory", "m0");
-}
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-constexpr int kX6Pitch = 272;                 // bytes per LDS row of one bf16 plane (128 k): conflict-free b128 reads
-constexpr int kX6Plane = kTR * kX6Pitch;      // one plane of a 64-row chunk
-constexpr int kX6Buf = 3 * kX6Plane;          // three planes (also holds the 64 x 128 fp32 exchange tile)
-constexpr int kX6Lds = 2 * kX6Buf;            // double-buffered
-// fp16 two-plane variant (K = 128 kernels): two planes, then the 64 inverse row scales of the chunk
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-constexpr int kH3Plane = kTR * kX6Pitch;      // same row pitch as the bf16 planes
+constexpr int kH3Pitch = 272;                 // bytes per LDS row of one fp16 plane (128 k): conflict-free b128 reads
+// LDS image of a 64-row chunk: two fp16 planes (hi, lo), then the 64 inverse row scales of the chunk
+constexpr int kH3Plane = kTR * kH3Pitch;
 constexpr int kH3Rs = 2 * kH3Plane;           // byte offset of float inv_row_scale[64] (past the 32 KiB exchange tile)
 constexpr int kH3Buf = kH3Rs + kTR * 4;
 constexpr int kH3Lds = 2 * kH3Buf;
 static_assert(kH3Rs >= kTR * 128 * 4, "the fp32 exchange tile must not reach the row scales");
-
-__device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
-    h = static_cast<__bf16>(x);
-    const float r1 = x - static_cast<float>(h);
-    m = static_cast<__bf16>(r1);
-    l = static_cast<__bf16>(r1 - static_cast<float>(m));
-}
-
-__global__ void pack_weight_x6_kernel(const float* __restrict__ w, bf16x8* __restrict__ p, int rows, int cols, int mode,
-                                      int n_tiles, int k_steps) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;   // one (slab, k-step, lane)
-    if (idx >= n_tiles * k_steps * 64) return;
-    const int lane = idx & 63, ks = (idx >> 6) % k_steps, t = (idx >> 6) / k_steps;
-    const int n = 32 * t + (lane & 31);
-    bf16x8 out[3];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int k = ks * 16 + 8 * (lane >> 5) + j;
-        float v;
-        if (mode == 0) v = (n < rows && k < cols) ? w[static_cast<size_t>(n) * cols + k] : 0.f;
-        else v = (k < rows && n < cols) ? w[static_cast<size_t>(k) * cols + n] : 0.f;
-        __bf16 h, m, l;
-        split3(v, h, m, l);
-        out[0][j] = h;
-        out[1][j] = m;
-        out[2][j] = l;
-    }
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) p[(static_cast<size_t>(t * k_steps + ks) * 3 + pl) * 64 + lane] = out[pl];
-}
 
 // ---- fp16 x 3: power-of-two scaled two-plane split -------------------------------------------------------
 // A row a (and a weight column w) is multiplied by a power of two that brings its largest magnitude into
@@ -477,20 +89,9 @@ __global__ void pack_weight_x6_kernel(const float* __restrict__ w, bf16x8* __res
 // elements lose bits only below 2^-39 of the maximum).  a.w ~= hi.hi + hi.lo + lo.hi with fp32
 // accumulation (the dropped lo.lo term is 2^-22 relative): three MFMAs per product instead of the six of
 // the bf16 three-plane split, two LDS planes instead of three, and the same fp32-class error (measured
-// against fp64 in tests/test_hip_kernels.py).  The epilogue multiplies by the inverse scales.
-__device__ __forceinline__ unsigned scale_exponent(float absmax) {   // biased exponent, clamped away from 0
-    const unsigned e = __float_as_uint(absmax) >> 23;
-    return e < 15u ? 15u : e;
-}
-__device__ __forceinline__ float scale_of(unsigned e) { return __uint_as_float((268u - e) << 23); }      // 2^(14 - (e - 127))
-__device__ __forceinline__ float inv_scale_of(unsigned e) { return __uint_as_float((e - 14u) << 23); }
-__device__ __forceinline__ float comp(const float4& v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
-// unsigned max steps (the ordering of |float| bit patterns): 0 is the identity, so the DPP move folds into v_max_u32
-template <int CTRL>
-__device__ __forceinline__ unsigned dpp_umax_step(unsigned x) {
-    const unsigned moved = static_cast<unsigned>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), CTRL, 0xF, 0xF, true));
-    return x > moved ? x : moved;
-}
+// against fp64 in tests/test_hip_kernels.py).  The epilogue multiplies by the inverse scales
+// (f16_scale.h).
+
 // Producer side of the fp16x3 kernels: thread `pt` holds PFN float4s, the i-th belonging to tile row (pt + STRIDE i) >> 5
 // at float4 column (pt & 31) (the 32 lanes of a half-wave hold one 128-wide row).  Row maximum -> power-of-two scale
 // -> hi / lo fp16 planes + the inverse scale, written to the LDS image `pl`.  The work is staged across groups of
@@ -500,7 +101,7 @@ template <int PFN, int STRIDE>
 __device__ __forceinline__ void split_write_h3(const float4 (&set)[PFN], char* pl, int pt) {
     constexpr int G = PFN > 8 ? 2 : 4;   // the 16-float4 producers (two waves) are short of registers
     static_assert(PFN % G == 0 && STRIDE % 32 == 0, "whole groups, whole rows");
-    char* const prow = pl + (pt >> 5) * kX6Pitch + (pt & 31) * 8;
+    char* const prow = pl + (pt >> 5) * kH3Pitch + (pt & 31) * 8;
     char* const prs = pl + kH3Rs + (pt >> 5) * 4;
 #pragma unroll
     for (int g0 = 0; g0 < PFN; g0 += G) {
@@ -514,13 +115,13 @@ __device__ __forceinline__ void split_write_h3(const float4 (&set)[PFN], char* p
             m[j] = __float_as_uint(u);
         }
 #pragma unroll
-        for (int j = 0; j < G; ++j) m[j] = dpp_umax_step<0xB1>(m[j]);
+        for (int j = 0; j < G; ++j) m[j] = umax_dpp<0xB1>(m[j]);
 #pragma unroll
-        for (int j = 0; j < G; ++j) m[j] = dpp_umax_step<0x4E>(m[j]);
+        for (int j = 0; j < G; ++j) m[j] = umax_dpp<0x4E>(m[j]);
 #pragma unroll
-        for (int j = 0; j < G; ++j) m[j] = dpp_umax_step<0x141>(m[j]);
+        for (int j = 0; j < G; ++j) m[j] = umax_dpp<0x141>(m[j]);
 #pragma unroll
-        for (int j = 0; j < G; ++j) m[j] = dpp_umax_step<0x140>(m[j]);
+        for (int j = 0; j < G; ++j) m[j] = umax_dpp<0x140>(m[j]);
         float sc[G];
 #pragma unroll
         for (int j = 0; j < G; ++j) {
@@ -554,8 +155,8 @@ __device__ __forceinline__ void split_write_h3(const float4 (&set)[PFN], char* p
             const f16x2 la = __builtin_convertvector(xa[j], f16x2), lb = __builtin_convertvector(xb[j], f16x2);
             const u32x2 h = {__builtin_bit_cast(unsigned, ha[j]), __builtin_bit_cast(unsigned, hb[j])};
             const u32x2 l = {__builtin_bit_cast(unsigned, la), __builtin_bit_cast(unsigned, lb)};
-            *reinterpret_cast<u32x2*>(prow + 0 * kH3Plane + (STRIDE / 32) * (g0 + j) * kX6Pitch) = h;
-            *reinterpret_cast<u32x2*>(prow + 1 * kH3Plane + (STRIDE / 32) * (g0 + j) * kX6Pitch) = l;
+            *reinterpret_cast<u32x2*>(prow + 0 * kH3Plane + (STRIDE / 32) * (g0 + j) * kH3Pitch) = h;
+            *reinterpret_cast<u32x2*>(prow + 1 * kH3Plane + (STRIDE / 32) * (g0 + j) * kH3Pitch) = l;
         }
         if ((pt & 31) == 0) {   // one divergent block per group (branches between the stages would serialise the chains)
 #pragma unroll
@@ -637,49 +238,26 @@ __global__ __launch_bounds__(512) void pack_weight_h3_batch_kernel(const long lo
                          nt, blockIdx.x, blockIdx.y, kc);
 }
 
-// exact three-way split of a float4 into bf16 planes by truncation: h = top 16 bits of x,
-// m = top 16 bits of (x - h), l = top 16 bits of (x - h - m); every remainder is exact and
-// h + m + l covers all 24 significand bits.  v_perm_b32 packs the high halves of a pair.
-__device__ __forceinline__ void split4(const float4& v, u32x2& h, u32x2& m, u32x2& l) {
-    const float x[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const unsigned a0 = __float_as_uint(x[2 * i]), a1 = __float_as_uint(x[2 * i + 1]);
-        h[i] = __builtin_amdgcn_perm(a1, a0, 0x07060302u);
-        const float r0 = x[2 * i] - __uint_as_float(a0 & 0xFFFF0000u);
-        const float r1 = x[2 * i + 1] - __uint_as_float(a1 & 0xFFFF0000u);
-        const unsigned b0 = __float_as_uint(r0), b1 = __float_as_uint(r1);
-        m[i] = __builtin_amdgcn_perm(b1, b0, 0x07060302u);
-        const float s0 = r0 - __uint_as_float(b0 & 0xFFFF0000u);
-        const float s1 = r1 - __uint_as_float(b1 & 0xFFFF0000u);
-        l[i] = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302u);
-    }
-}
-
 // Workgroup program: 8 waves, one workgroup per CU, persistent over 64-row tiles.
 //   waves 4..7  producers: stream A chunks (64 rows x 128 k fp32) HBM -> registers (three chunks deep,
-//               96 KiB in flight per CU) -> split -> three bf16 planes in LDS (double-buffered);
-//   waves 0..3  consumers: wave w = 32-column slab w of the current 128-column group: 6 MFMAs per
+//               96 KiB in flight per CU) -> split -> fp16 hi / lo planes in LDS (double-buffered);
+//   waves 0..3  consumers: wave w = 32-column slab w of the current 128-column group: 3 MFMAs per
 //               (k-step, 32-row block) on fragments read from the planes, then the epilogue.
-// One barrier per chunk separates "planes[c] written" from "planes[c] read".  K = 384: three chunks per
-// tile accumulate into the same registers; N = 384: the three column groups of a tile run back to back on
-// the same planes.  The B fragments of the current (group, chunk) live in 96 VGPRs; when they change
-// per unit they are double-buffered (the next unit's arrive from L2 during this unit's MFMAs).
-template <int KC, int NG, bool EXCH, int NC = 4, bool LNB = false, bool LNA = false, bool S3 = false>
+// One barrier per chunk separates "planes[c] written" from "planes[c] read".  K = 128: one chunk per tile.
+// NG = 3 (the three-output q / k / v launch): the three column groups of a tile run back to back on the same planes,
+// and the B fragments of a group (64 VGPRs, two halves) are double-buffered: the next group's arrive from L2 during
+// this group's MFMAs.  NG = 1: the B fragments stay resident.
+template <int NG, bool EXCH, bool LNB = false, bool LNA = false, bool S3 = false>
 __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __restrict__ a, const f16x8* __restrict__ packed,
                                                              float* __restrict__ y, int64_t R, Epilogue ep) {
-    // NC = 6 (N = 384 only): six consumer waves, each with two resident 32-column slabs (w and w + 6: 128 VGPRs
-    // of fp16 fragments), two producer waves: no B-fragment stream from L2, the A tile is read once and every
-    // A fragment read from LDS feeds two slabs.
-    constexpr int NM = 8 - NC, PFN = 2048 / (64 * NM);   // producer waves, float4 per producer thread and chunk
-    constexpr int K = KC * 128, KS = KC * 8, N = NC == 6 ? 384 : 128 * NG, UPT = KC * NG;
-    constexpr int SLABS = NC == 6 ? 12 : 4 * NG;   // 32-column slabs of the whole output (bit-mask layout)
-    constexpr int NS = NC == 6 ? 2 : 1;            // slabs per consumer wave
-    static_assert(NC == 4 || (NC == 6 && KC == 1 && NG == 1 && !EXCH), "6 consumers: resident-B 128 -> 384 only");
-    static_assert(KC == 1, "fp16x3: the row scale covers the whole contraction, K = 128 only");
-    static_assert(!LNB || (EXCH && NC == 4 && NG == 1), "LayerNorm-backward epilogue: 128 -> 128 exchange kernel");
-    static_assert(!LNA || (!EXCH && !LNB && NC == 4 && NG == 1), "LayerNorm-backward prologue: plain 128 -> 128 kernel");
-    static_assert(!S3 || (NG == 3 && NC == 4 && !EXCH), "three outputs: the streaming-B 128 -> 384 kernel (one column group per Linear)");
+    // K = 128: one chunk per tile, the row scale covers the whole contraction
+    constexpr int NC = 4, NM = 8 - NC, PFN = 2048 / (64 * NM);   // consumer / producer waves, float4 per producer thread and chunk
+    constexpr int K = 128, KS = 8, N = 128 * NG;
+    constexpr int SLABS = 4 * NG;   // 32-column slabs of the whole output (bit-mask layout)
+    constexpr int NS = 1;           // slabs per consumer wave (the loops over it shape hipcc's schedule of the NG = 3 instance)
+    static_assert(!LNB || (EXCH && NG == 1), "LayerNorm-backward epilogue: 128 -> 128 exchange kernel");
+    static_assert(!LNA || (!EXCH && !LNB && NG == 1), "LayerNorm-backward prologue: plain 128 -> 128 kernel");
+    static_assert(!S3 || (NG == 3 && !EXCH), "three outputs: the streaming-B 128 -> 384 kernel (one column group per Linear)");
     constexpr int DEPTH = LNA ? 2 : 3;      // register sets of A chunks the producers keep in flight
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     char* lds = smem_raw;                              // 2 x { planes[2][64 rows][272 B], inv_row_scale[64] }
@@ -690,18 +268,17 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
     const int64_t tiles = (R + kTR - 1) / kTR;
     if (static_cast<int64_t>(blockIdx.x) >= tiles) return;
     const int64_t my_tiles = (tiles - blockIdx.x + gridDim.x - 1) / gridDim.x;
-    const int64_t nchunks = my_tiles * KC;
-    // Workgroups walk the three k-chunks / column groups of a tile in rotated orders (blockIdx % 3): at any
+    const int64_t nchunks = my_tiles;      // one 128-wide chunk per tile
+    // Workgroups walk the three column groups of a tile in rotated orders (blockIdx % 3): at any
     // moment a third of the CUs streams each group's B fragments from L2 instead of all CUs the same 96 KiB.
     const int rot = static_cast<int>(blockIdx.x % 3);
     const int64_t padded = (nchunks + DEPTH - 1) / DEPTH * DEPTH;      // the producers run whole groups of DEPTH iterations
     // tiles round-robin over the workgroups, ascending or (ep.reverse, traversal.h) descending
     auto tile_at = [&](int64_t ti) {
         const int64_t t = blockIdx.x + ti * gridDim.x;
-        if constexpr (LNB || LNA || S3 || NC != 4) return t;      // (partial sums per workgroup / node-level kernels: always ascending)
+        if constexpr (LNB || LNA || S3) return t;      // (partial sums per workgroup / node-level kernels: always ascending)
         else return ep.reverse ? tiles - 1 - t : t;
     };
-    auto tile_of = [&](int64_t chunk) { return tile_at(chunk / KC); };
 
     if (w >= NC) {
         // ------------------------------------------------------------------ producers
@@ -721,7 +298,7 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
             float4 dgam = f4(0.f), dbet = f4(0.f);
             const unsigned voff0 = static_cast<unsigned>(pt >> 5) * (K_ * 4) + static_cast<unsigned>(pt & 31) * 16;
             auto offsets = [&](int64_t chunk, int64_t& r0, unsigned& lim) {
-                r0 = tile_of(chunk) * kTR;
+                r0 = tile_at(chunk) * kTR;
                 const int64_t last = R - 1 - r0;   // >= 0
                 lim = last >= kTR - 1 ? 0xFFFFFFFFu
                                       : static_cast<unsigned>(last) * (K_ * 4) + static_cast<unsigned>(pt & 31) * 16;
@@ -834,7 +411,7 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
         const unsigned voff0 = static_cast<unsigned>(pt >> 5) * (K * 4) + static_cast<unsigned>(pt & 31) * 16;
         auto fetch = [&](float4 (&set)[PFN], int64_t chunk) {
             if (chunk > nchunks - 1) chunk = nchunks - 1;
-            const int64_t r0 = tile_of(chunk) * kTR;
+            const int64_t r0 = tile_at(chunk) * kTR;
             const char* base = reinterpret_cast<const char*>(a) + r0 * (K * 4);
             const int64_t last = R - 1 - r0;   // >= 0
             const unsigned lim = last >= kTR - 1 ? 0xFFFFFFFFu
@@ -851,7 +428,7 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
             split_write_h3<PFN, 64 * NM>(set, lds + (chunk & 1) * kH3Buf, pt);
         };
         auto end_of_iteration = [&](int64_t c) {
-            if (EXCH && c % KC == KC - 1 && c < nchunks) {   // the consumers' exchange epilogue: two more barriers
+            if (EXCH && c < nchunks) {   // the consumers' exchange epilogue: two more barriers
                 __syncthreads();
                 __syncthreads();
             }
@@ -896,15 +473,15 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
     // unit changes (K = 384 or N = 384) the halves form a ring: half 1 of this unit is requested from L2
     // at the start of the unit, half 0 of the next unit after the first four k-steps.
     f16x8 bset[2][NS][2][4];
-    auto slab_of = [&](int g, int s) { return NC == 6 ? w + 6 * s : 4 * g + w; };
-    auto load_b = [&](f16x8 (&bfr)[NS][2][4], int g, int kc, int h) {
+    auto slab_of = [&](int g, int) { return 4 * g + w; };      // (column group, slab of the wave)
+    auto load_b = [&](f16x8 (&bfr)[NS][2][4], int g, int h) {
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             const f16x8* wp = packed + static_cast<size_t>(slab_of(g, s)) * KS * 2 * 64 + lane;
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
-                for (int p = 0; p < 2; ++p) bfr[s][p][ks] = wp[((kc * 8 + 4 * h + ks) * 2 + p) * 64];
+                for (int p = 0; p < 2; ++p) bfr[s][p][ks] = wp[((4 * h + ks) * 2 + p) * 64];
         }
     };
     const float* inv_cs = reinterpret_cast<const float*>(packed + static_cast<size_t>(SLABS) * KS * 2 * 64);
@@ -931,17 +508,16 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
 #endif
     // one unit = one (chunk, column group): MFMAs on planes[chunk & 1] with `bfr`, epilogue when the
     // contraction is complete; `bnext` receives the B fragments of the following unit meanwhile
-    auto unit = [&](int64_t ti, int pos_kc, int pos_g) {   // positions within the tile; values are rotated
-        const int kc = pos_kc, kcv = KC > 1 ? (pos_kc + rot) % KC : 0;
+    auto unit = [&](int64_t ti, int pos_g) {   // positions within the tile; values are rotated
         const int g = NG > 1 ? (pos_g + rot) % NG : 0;
-        const int64_t chunk = ti * KC + pos_kc;
+        const int64_t chunk = ti;
         const int64_t tix = tile_at(ti);
         const int64_t r0 = tix * kTR;
-        if (UPT > 1) load_b(bset[1], g, kcv, 1);
+        if (NG > 1) load_b(bset[1], g, 1);
         // ReLU mask words of this unit's slabs, requested before the MFMA phase and unconditionally (a null mask reads a
         // valid dummy word): a load inside the epilogue would be awaited with vmcnt(0) -- i.e. behind the stores
         // the previous slab has just issued -- once per slab, whether or not a mask is present
-        constexpr bool BITS_IN = !EXCH && (NG == 3 || NC == 6);
+        constexpr bool BITS_IN = !EXCH && NG == 3;
         unsigned mask_in[NS];
         if (BITS_IN) {
 #pragma unroll
@@ -951,14 +527,12 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
                 mask_in[s] = *mp;
             }
         }
-        if (kc == 0) {
 #pragma unroll
-            for (int s = 0; s < NS; ++s)
+        for (int s = 0; s < NS; ++s)
 #pragma unroll
-                for (int m = 0; m < 2; ++m)
+            for (int m = 0; m < 2; ++m)
 #pragma unroll
-                    for (int i = 0; i < 16; ++i) acc[s][m][i] = 0.f;
-        }
+                for (int i = 0; i < 16; ++i) acc[s][m][i] = 0.f;
         // rows of this wave in the exchange epilogue: w * 16 + it * 2 + half, clamped to the last row of a partial tile
         // in 32 bits: uniform 64-bit tile base + a per-lane byte offset derived HERE from lane terms that are opaque per
         // tile (as loop invariants the per-row pointers are hoisted out of the tile loop and spilled)
@@ -970,7 +544,7 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
             rr = rr < lastr ? rr : lastr;
             return rr * 512u + colv * 16u;
         };
-        if (EXCH && kc == KC - 1 && ep.residual) {
+        if (EXCH && ep.residual) {
             const char* rbase = reinterpret_cast<const char*>(ep.residual) + r0 * 512;
 #pragma unroll
             for (int it = 0; it < 8; ++it) res[it] = ld4(reinterpret_cast<const float*>(rbase + row_off(it)));
@@ -984,7 +558,7 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
             for (int m = 0; m < 2; ++m)
 #pragma unroll
                 for (int p = 0; p < 2; ++p)
-                    dst[m][p] = *reinterpret_cast<const f16x8*>(pl + p * kH3Plane + (32 * m + col) * kX6Pitch +
+                    dst[m][p] = *reinterpret_cast<const f16x8*>(pl + p * kH3Plane + (32 * m + col) * kH3Pitch +
                                                                 (ks * 16 + 8 * half) * 2);
         };
         // inverse scales of this lane's accumulator rows: 32 m + 8 q + 4 half + (0..3), times the column's
@@ -997,9 +571,9 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
             if (ks + 1 < 8) frags(ks + 1, af[(ks + 1) & 1]);
-            if (UPT > 1 && ks == 4) {   // half 0 is consumed: request the next unit's (same tile or next)
-                const int un = (pos_kc * NG + pos_g + 1) % UPT;   // next position: same tile, or the next tile's first
-                load_b(bset[0], NG > 1 ? (un + rot) % NG : 0, KC > 1 ? (un + rot) % KC : 0, 0);
+            if (NG > 1 && ks == 4) {   // half 0 is consumed: request the next unit's (same tile or next)
+                const int un = (pos_g + 1) % NG;   // next position: same tile, or the next tile's first
+                load_b(bset[0], (un + rot) % NG, 0);
             }
             const f16x8(&f)[2][2] = af[ks & 1];
             const f16x8(&bfr)[NS][2][4] = bset[ks >> 2];
@@ -1021,9 +595,9 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
         // ago) tells the compiler's scoreboard that every earlier load is back: the slabs' stores then stream without a
         // wait between them (128 -> 384: 310 -> 296 us at R = 518 400, A/B in one call).
         if (BITS_IN) wait_all_vmem_visible();
-        if (!EXCH && kc == KC - 1) {
+        if (!EXCH) {
             // direct epilogue from the accumulator layout, one (slab, 32-row block) at a time
-            constexpr bool BITS = NG == 3 || NC == 6;   // ReLU bit masks in / out: only the fc1-shaped launches use them
+            constexpr bool BITS = NG == 3;   // ReLU bit masks in / out: only the fc1-shaped launches use them
             const bool full = r0 + kTR <= R;
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
@@ -1084,7 +658,7 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
                 if (BITS && ep.relu_bits) ep.relu_bits[bix] = newbits;
             }
         }
-        if (EXCH && kc == KC - 1) {
+        if (EXCH) {
             // exchange through the consumed planes so that each half-wave finalises whole 512-byte rows
             float* ex = reinterpret_cast<float*>(lds + (chunk & 1) * kH3Buf);
             const float bias = bias_g[0];
@@ -1215,18 +789,18 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
         if (pos_g == NG - 1) __syncthreads();   // end of this chunk's iteration
         GSTAMP(tB)
     };
-    load_b(bset[0], NG > 1 ? rot : 0, KC > 1 ? rot : 0, 0);
-    if (UPT == 1) load_b(bset[1], 0, 0, 1);
+    load_b(bset[0], NG > 1 ? rot : 0, 0);
+    if (NG == 1) load_b(bset[1], 0, 1);
     __syncthreads();   // chunk 0 is in planes[0]
 #if DG_DBG & 16
     tl = t00 = __builtin_amdgcn_s_memtime();
 #endif
     for (int64_t ti = 0; ti < my_tiles; ++ti) {
-        if constexpr (UPT == 1) {
-            unit(ti, 0, 0);
+        if constexpr (NG == 1) {
+            unit(ti, 0);
         } else {   // rolled on purpose: three inlined copies let hipcc hoist loads across units and spill
 #pragma unroll 1
-            for (int u = 0; u < UPT; ++u) unit(ti, KC > 1 ? u : 0, NG > 1 ? u : 0);
+            for (int u = 0; u < NG; ++u) unit(ti, u);
         }
     }
     for (int64_t c = nchunks; c < padded; ++c) __syncthreads();   // match the producers' padded iterations
@@ -1255,7 +829,7 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
 //   * refills the fragments by hand: the load of a k-step's registers is issued right after their last
 //     MFMA in the second unit of a position, the first unit of the next position waits per k-step with the
 //     exact in-order count (3 (7 - ks) younger loads) -- the consumers issue no other VMEM operation;
-//   * keeps every global access in waves 4..7: A chunks HBM -> registers (three deep) -> split -> bf16
+//   * keeps every global access in waves 4..7: A chunks HBM -> registers (three deep) -> split -> fp16
 //     planes, and the finished tile's epilogue (exchange tile in LDS -> residual / LayerNorm -> 512-byte
 //     row stores).  Their loop is one straight line per tile pair so that hipcc can count loads in flight.
 // Barriers: B(c) ends every chunk; A(c) precedes the exchange-tile write of a chunk that completes a tile.
@@ -1267,10 +841,10 @@ __device__ __forceinline__ void wait_b_refill(f16x8& b0, f16x8& b1) {
     asm volatile("s_waitcnt vmcnt(%2)" : "+v"(b0), "+v"(b1) : "n"(N));
 }
 
-template <bool EXCH, bool A3 = false>
+template <bool EXCH>
 __global__ __launch_bounds__(512, 2) void row_gemm_h3_k384_kernel(const float* __restrict__ a, const f16x8* __restrict__ packed,
                                                                   float* __restrict__ y, int64_t R, Epilogue ep) {
-    constexpr int KC = 3, K = 384, KS = 24;
+    constexpr int KC = 3, KS = 24;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     char* lds = smem_raw;                                          // 2 x { planes[2][64 rows][272 B], inv_row_scale[64] }
     float* ex = reinterpret_cast<float*>(smem_raw + 2 * kH3Buf);   // exchange tile [64][128] fp32
@@ -1302,8 +876,8 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_k384_kernel(const float* _
         float4 pf[3][8];
         // loads of a chunk: uniform 64-bit base (tile, k chunk) + a 32-bit per-lane byte offset; rows past the end
         // of a partial tile are clamped on the offset (row-major, so the row term dominates the comparison)
-        // A3: the three k-chunks are three separate [R,128] matrices (row pitch 512 B) instead of column blocks of one [R,384]
-        constexpr int APITCH = A3 ? 512 : K * 4;
+        // the three k-chunks are three separate [R,128] matrices (row pitch 512 B), not column blocks of one [R,384]
+        constexpr int APITCH = 512;
         const unsigned voff0 = static_cast<unsigned>(pt >> 5) * APITCH + static_cast<unsigned>(pt & 31) * 16;
         auto fetch = [&](float4 (&set)[8], int c) {
             if (c > nchunks - 1) c = nchunks - 1;
@@ -1311,8 +885,7 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_k384_kernel(const float* _
             chunk_map(c, ti, pos);
             const int64_t r0 = tile_row0(ti);
             const int kc = (pos + rot) % KC;
-            const char* base = A3 ? reinterpret_cast<const char*>(kc == 0 ? a : ep.a_alt[kc - 1]) + r0 * 512
-                                  : reinterpret_cast<const char*>(a) + (r0 * K + kc * 128) * 4;
+            const char* base = reinterpret_cast<const char*>(kc == 0 ? a : ep.a_alt[kc - 1]) + r0 * 512;
             const int64_t last = R - 1 - r0;   // >= 0
             const unsigned lim = last >= kTR - 1 ? 0xFFFFFFFFu : static_cast<unsigned>(last) * APITCH + static_cast<unsigned>(pt & 31) * 16;
 #pragma unroll
@@ -1330,7 +903,7 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_k384_kernel(const float* _
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     const int L = pt + 256 * i, r = L >> 5, c4 = L & 31;
-                    *reinterpret_cast<float4*>(pl + (i & 1) * kH3Plane + r * kX6Pitch + (c4 >> 1) * 16) = set[i];
+                    *reinterpret_cast<float4*>(pl + (i & 1) * kH3Plane + r * kH3Pitch + (c4 >> 1) * 16) = set[i];
                 }
             } else {
                 split_write_h3<8, 256>(set, lds + (c & 1) * kH3Buf, pt);
@@ -1495,7 +1068,7 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_k384_kernel(const float* _
             for (int m = 0; m < 2; ++m)
 #pragma unroll
                 for (int p = 0; p < 2; ++p)
-                    dst[m][p] = *reinterpret_cast<const f16x8*>(pl + p * kH3Plane + (32 * m + col) * kX6Pitch +
+                    dst[m][p] = *reinterpret_cast<const f16x8*>(pl + p * kH3Plane + (32 * m + col) * kH3Pitch +
                                                                 (ks * 16 + 8 * half) * 2);
         };
         f32x16 part[2];   // this chunk's products; folded into `acc` with the chunk's inverse row scales
@@ -1602,10 +1175,6 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_k384_kernel(const float* _
 
 namespace dg {
 
-// The float32 row GEMMs run the fp16 hi + lo arithmetic (three MFMA products); the v_mfma_f32_32x32x2_f32 kernels of round 1
-// are no longer launched.
-static constexpr bool use_x6() { return true; }
-
 size_t row_gemm_f32_packed_floats(int n_out, int k_contract) {
     if (n_out < 1 || k_contract < 1) return 0;
     const size_t nt = (n_out + 31) / 32, kc = (k_contract + 127) / 128;
@@ -1615,8 +1184,8 @@ size_t row_gemm_f32_packed_floats(int n_out, int k_contract) {
 int row_gemm_f32_pack(const float* w, float* packed, int rows, int cols, int mode, dg_stream_t stream_,
                       const float* w1, const float* w2) {
     if (!w || !packed) return fail(DG_E_ARG, "dg_row_gemm_pack: null pointer");
-    if ((w1 || w2) && (!w1 || !w2 || rows != 384 || !use_x6()))
-        return fail(DG_E_ARG, "dg_row_gemm_pack3: needs three [128, cols] weights (and the fp16 hi+lo row GEMM)");
+    if ((w1 || w2) && (!w1 || !w2 || rows != 384))
+        return fail(DG_E_ARG, "dg_row_gemm_pack3: needs three [128, cols] weights");
     if (mode != 0 && mode != 1) return fail(DG_E_ARG, "dg_row_gemm_pack: mode must be 0 (forward) or 1 (dgrad)");
     const int n_out = mode == 0 ? rows : cols, k = mode == 0 ? cols : rows;
     const int nt = (n_out + 31) / 32, kc = (k + 127) / 128;
@@ -1628,7 +1197,6 @@ int row_gemm_f32_pack(const float* w, float* packed, int rows, int cols, int mod
 int row_gemm_f32_pack_batch(const void* table, int n, int max_rows_cols, dg_stream_t stream_) {
     if (!table) return fail(DG_E_ARG, "dg_row_gemm_pack_batch: null pointer");
     if (n < 1) return 0;
-    if (!use_x6()) return fail(DG_E_ARG, "dg_row_gemm_pack_batch: needs the fp16 hi+lo row GEMM (DG_ROW_GEMM=mfma32 is set)");
     const int nt = (max_rows_cols + 31) / 32, kc = (max_rows_cols + 127) / 128;
     hipLaunchKernelGGL(pack_weight_h3_batch_kernel, dim3(nt, kc, n), dim3(512), 0, static_cast<hipStream_t>(stream_),
                        static_cast<const long long*>(table));
@@ -1659,45 +1227,36 @@ int row_gemm_f32(const float* a, const float* packed, float* y, int64_t R, int K
     if ((mask_bits || relu_bits_out) && K != 128)
         return fail(DG_E_ARG, "dg_row_gemm: bit masks need K == 128");
     if (exch && N != 128) return fail(DG_E_ARG, "dg_row_gemm: residual / LayerNorm epilogues need N == 128");
-    if (use_x6() && (mask_bits || relu_bits_out) && N != 384)
+    if ((mask_bits || relu_bits_out) && N != 384)
         return fail(DG_E_ARG, "dg_row_gemm: bit masks need the 128 -> 384 shape");
     if (R == 0) return 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     Epilogue ep{bias, mask_bits, relu_bits_out, residual, gamma, beta, mean, rstd, pre_ln, eps, relu};
     ProfScope prof(R < edge_rows() ? DG_K_ROW_GEMM : (K == 384 ? DG_K_ROW_GEMM_E_K384 : (N == 384 ? DG_K_ROW_GEMM_E_N384 : DG_K_ROW_GEMM_E_128)), stream);
-    if (use_x6()) {
-        const int ng = N / 128;
-        const int64_t tiles = (R + kTR - 1) / kTR;
-        int seqs = 256;                             // one 8-wave workgroup per CU
-        if (tiles < seqs) seqs = static_cast<int>(tiles);
-        (void)ng;
-#define LAUNCH6(KC_, NG_, EX_)                                                                                     \
-    {                                                                                                              \
-        constexpr int lds_ = kH3Lds + (EX_ ? 0 : 4 * 32 * 32 * 4);                                                \
-        DG_OPT_IN_LDS((&row_gemm_h3_kernel<KC_, NG_, EX_>), lds_);                                                 \
-        hipLaunchKernelGGL((row_gemm_h3_kernel<KC_, NG_, EX_>), dim3(seqs), dim3(512), lds_, stream, a,            \
-                           reinterpret_cast<const f16x8*>(packed), y, R, ep);                                      \
+    // 128 -> 384: the producer / consumer kernel (row_gemm_n384.hip)
+    if (K == 128 && N == 384) {
+        if (int st = launch_row_gemm_n384(a, packed, y, yscale, R, bias, relu, relu_bits_out, mask_bits, stream, yfmt, ylo)) return st;
+        return check_launch("dg_row_gemm");
     }
-        // 128 -> 384: the producer / consumer kernel (row_gemm_n384.hip)
-        if (K == 128 && N == 384) {
-            if (int st = launch_row_gemm_n384(a, packed, y, yscale, R, bias, relu, relu_bits_out, mask_bits, stream, yfmt, ylo)) return st;
-            return check_launch("dg_row_gemm");
-        }
-        // 384 -> 128: the producer / consumer kernel (row_gemm_k384.hip)
-        if (K == 384) {
-            if (int st = launch_row_gemm_k384(a, ascale, packed, y, R, bias, relu, residual, gamma, beta, mean, rstd, pre_ln, eps, stream, afmt, alo))
-                return st;
-            return check_launch("dg_row_gemm");
-        }
-        if (K == 128 && exch) {
-            ep.reverse = take_direction(R);
-            LAUNCH6(1, 1, true)
-        } else {
-            ep.reverse = take_direction(R);
-            LAUNCH6(1, 1, false)
-        }
-#undef LAUNCH6
+    // 384 -> 128: the producer / consumer kernel (row_gemm_k384.hip)
+    if (K == 384) {
+        if (int st = launch_row_gemm_k384(a, ascale, packed, y, R, bias, relu, residual, gamma, beta, mean, rstd, pre_ln, eps, stream, afmt, alo))
+            return st;
+        return check_launch("dg_row_gemm");
     }
+    const int64_t tiles = (R + kTR - 1) / kTR;
+    const int seqs = static_cast<int>(tiles < 256 ? tiles : 256);      // one 8-wave workgroup per CU
+    ep.reverse = take_direction(R);
+#define LAUNCH_H3(EX_)                                                                                         \
+    {                                                                                                          \
+        constexpr int lds_ = kH3Lds + (EX_ ? 0 : 4 * 32 * 32 * 4);                                            \
+        DG_OPT_IN_LDS((&row_gemm_h3_kernel<1, EX_>), lds_);                                                    \
+        hipLaunchKernelGGL((row_gemm_h3_kernel<1, EX_>), dim3(seqs), dim3(512), lds_, stream, a,               \
+                           reinterpret_cast<const f16x8*>(packed), y, R, ep);                                  \
+    }
+    if (exch) LAUNCH_H3(true)
+    else LAUNCH_H3(false)
+#undef LAUNCH_H3
     return check_launch("dg_row_gemm");
 }
 
@@ -1715,7 +1274,6 @@ int row_gemm_f32_ln_bwd(const float* a, const float* packed, float* dz, int64_t 
     // (384 -> 128: the epilogue of that kernel runs in its producer waves, which already hold three A chunks in
     // registers: built, 593 us against 302 + 161 us for the two launches at R = 518 400 -- not kept)
     if (R < 0 || K != 128) return fail(DG_E_SHAPE, "dg_row_gemm_ln_bwd: unsupported K=%d (K = N = 128)", K);
-    if (!use_x6()) return fail(DG_E_ARG, "dg_row_gemm_ln_bwd: needs the fp16 hi+lo row GEMM (DG_ROW_GEMM=mfma32 is set)");
     if (workspace_bytes < row_gemm_f32_ln_bwd_workspace_bytes()) return fail(DG_E_WORKSPACE, "dg_row_gemm_ln_bwd: workspace too small");
     if (R == 0) return 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -1727,8 +1285,8 @@ int row_gemm_f32_ln_bwd(const float* a, const float* packed, float* dz, int64_t 
     {
         ProfScope prof(R < edge_rows() ? DG_K_ROW_GEMM : DG_K_ROW_GEMM_E_128, stream);
         note_forward(R);      // (dgamma / dbeta partial sums: the order of the rows matters)
-        DG_OPT_IN_LDS((&row_gemm_h3_kernel<1, 1, true, 4, true>), kH3Lds);
-        hipLaunchKernelGGL((row_gemm_h3_kernel<1, 1, true, 4, true>), dim3(seqs), dim3(512), kH3Lds, stream, a,
+        DG_OPT_IN_LDS((&row_gemm_h3_kernel<1, true, true>), kH3Lds);
+        hipLaunchKernelGGL((row_gemm_h3_kernel<1, true, true>), dim3(seqs), dim3(512), kH3Lds, stream, a,
                            reinterpret_cast<const f16x8*>(packed), dz, R, ep);
     }
     if (dgamma || dbeta) launch_ln_finish(ep.lnb_part, seqs * 8, 2, 128, dgamma, dbeta, stream);
@@ -1745,7 +1303,6 @@ int row_gemm_f32_ln_in(const float* dy, const float* pre, const float* mean, con
     if (!dy || !pre || !mean || !rstd || !gamma || !packed || !dz || !y || !workspace)
         return fail(DG_E_ARG, "dg_row_gemm_ln_bwd_in: null pointer");
     if (R < 0) return fail(DG_E_SHAPE, "dg_row_gemm_ln_bwd_in: R = %lld", static_cast<long long>(R));
-    if (!use_x6()) return fail(DG_E_ARG, "dg_row_gemm_ln_bwd_in: needs the fp16 hi+lo row GEMM (DG_ROW_GEMM=mfma32 is set)");
     if (workspace_bytes < row_gemm_f32_ln_bwd_workspace_bytes()) return fail(DG_E_WORKSPACE, "dg_row_gemm_ln_bwd_in: workspace too small");
     if (R == 0) return 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -1759,8 +1316,8 @@ int row_gemm_f32_ln_in(const float* dy, const float* pre, const float* mean, con
         ProfScope prof(R < edge_rows() ? DG_K_ROW_GEMM : DG_K_ROW_GEMM_E_128, stream);
         note_forward(R);      // (dgamma / dbeta partial sums: the order of the rows matters)
         constexpr int lds = kH3Lds + 4 * 32 * 32 * 4;
-        DG_OPT_IN_LDS((&row_gemm_h3_kernel<1, 1, false, 4, false, true>), lds);
-        hipLaunchKernelGGL((row_gemm_h3_kernel<1, 1, false, 4, false, true>), dim3(seqs), dim3(512), lds, stream, dy,
+        DG_OPT_IN_LDS((&row_gemm_h3_kernel<1, false, false, true>), lds);
+        hipLaunchKernelGGL((row_gemm_h3_kernel<1, false, false, true>), dim3(seqs), dim3(512), lds, stream, dy,
                            reinterpret_cast<const f16x8*>(packed), y, R, ep);
     }
     // inside dg_linear_wgrad_batch_begin / _end the reduction joins that batch's launch (dgamma, dbeta adjacent)
@@ -1776,7 +1333,6 @@ int row_gemm_f32_lin3(const float* a, const float* packed, float* y0, float* y1,
                       const float* b1, const float* b2, dg_stream_t stream_) {
     if (!a || !packed || !y0 || !y1 || !y2) return fail(DG_E_ARG, "dg_row_gemm_lin3: null pointer");
     if (R < 0) return fail(DG_E_SHAPE, "dg_row_gemm_lin3: negative row count");
-    if (!use_x6()) return fail(DG_E_ARG, "dg_row_gemm_lin3: needs the fp16 hi+lo row GEMM (DG_ROW_GEMM=mfma32 is set)");
     if (R == 0) return 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     Epilogue ep{b0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0};
@@ -1791,8 +1347,8 @@ int row_gemm_f32_lin3(const float* a, const float* packed, float* y0, float* y1,
     // the column-group kernel (B fragments streamed per group: these launches are node-level, one or two tiles per
     // workgroup, where residency buys nothing; the resident-B instance with three outputs spills 168 B / lane)
     constexpr int lds3 = kH3Lds + 4 * 32 * 32 * 4;
-    DG_OPT_IN_LDS((&row_gemm_h3_kernel<1, 3, false, 4, false, false, true>), lds3);
-    hipLaunchKernelGGL((row_gemm_h3_kernel<1, 3, false, 4, false, false, true>), dim3(seqs), dim3(512), lds3, stream, a,
+    DG_OPT_IN_LDS((&row_gemm_h3_kernel<3, false, false, false, true>), lds3);
+    hipLaunchKernelGGL((row_gemm_h3_kernel<3, false, false, false, true>), dim3(seqs), dim3(512), lds3, stream, a,
                        reinterpret_cast<const f16x8*>(packed), y0, R, ep);
     return check_launch("dg_row_gemm_lin3");
 }
@@ -1803,7 +1359,6 @@ int row_gemm_f32_sum3(const float* a0, const float* a1, const float* a2, const f
                       const float* residual, dg_stream_t stream_) {
     if (!a0 || !a1 || !a2 || !packed || !y) return fail(DG_E_ARG, "dg_row_gemm_sum3: null pointer");
     if (R < 0) return fail(DG_E_SHAPE, "dg_row_gemm_sum3: negative row count");
-    if (!use_x6()) return fail(DG_E_ARG, "dg_row_gemm_sum3: needs the fp16 hi+lo row GEMM (DG_ROW_GEMM=mfma32 is set)");
     if (R == 0) return 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     Epilogue ep{nullptr, nullptr, nullptr, residual, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0};
@@ -1814,12 +1369,12 @@ int row_gemm_f32_sum3(const float* a0, const float* a1, const float* a2, const f
     ProfScope prof(R < edge_rows() ? DG_K_ROW_GEMM : DG_K_ROW_GEMM_E_K384, stream);
     constexpr int lds384 = 2 * kH3Buf + kTR * 128 * 4;
     if (residual) {
-        DG_OPT_IN_LDS((&row_gemm_h3_k384_kernel<true, true>), lds384);
-        hipLaunchKernelGGL((row_gemm_h3_k384_kernel<true, true>), dim3(seqs), dim3(512), lds384, stream, a0,
+        DG_OPT_IN_LDS((&row_gemm_h3_k384_kernel<true>), lds384);
+        hipLaunchKernelGGL((row_gemm_h3_k384_kernel<true>), dim3(seqs), dim3(512), lds384, stream, a0,
                            reinterpret_cast<const f16x8*>(packed), y, R, ep);
     } else {
-        DG_OPT_IN_LDS((&row_gemm_h3_k384_kernel<false, true>), lds384);
-        hipLaunchKernelGGL((row_gemm_h3_k384_kernel<false, true>), dim3(seqs), dim3(512), lds384, stream, a0,
+        DG_OPT_IN_LDS((&row_gemm_h3_k384_kernel<false>), lds384);
+        hipLaunchKernelGGL((row_gemm_h3_k384_kernel<false>), dim3(seqs), dim3(512), lds384, stream, a0,
                            reinterpret_cast<const f16x8*>(packed), y, R, ep);
     }
     return check_launch("dg_row_gemm_sum3");

@@ -28,6 +28,8 @@
 
 #include <cstdlib>
 #include "row_gemm_k384.h"
+#include "lane_reduce.h"
+#include "mfma_f16.h"
 #include "pair.h"
 #include "traversal.h"
 
@@ -37,13 +39,6 @@
 namespace dg {
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kSR = 16;                                  // rows per stage
 constexpr int kPlane = 48 * 256;                         // [chunk 3][k-step 4][k-quarter 4][row 16 (xor-swizzled)][16 B]
 constexpr int kStage = 2 * kPlane + 256;                 // hi, lo, inverse scales [16 rows][3 chunks] (+ pad)
@@ -52,43 +47,6 @@ constexpr int kOffOut = 2 * kStage;
 constexpr int kOffTab = kOffOut + 2 * kOut;              // gamma [128], beta [128]
 constexpr int kLds = kOffTab + 2 * 128 * 4;
 constexpr int kCons = 8, kProd = 4, kDepth = 3;
-
-template <int CTRL>
-__device__ __forceinline__ unsigned umax_dpp(unsigned x) {
-    const unsigned moved = static_cast<unsigned>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), CTRL, 0xF, 0xF, true));
-    return x > moved ? x : moved;
-}
-template <int CTRL>
-__device__ __forceinline__ float sum_dpp(float x) {
-    const int moved = __builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, true);
-    return x + __int_as_float(moved);
-}
-// sum over the 32 lanes of a half-wave, result in every lane (DPP inside the 16-lane rows, two scalar reads across)
-__device__ __forceinline__ float half_wave_total(float x, bool upper) {
-    x = sum_dpp<0xB1>(x);
-    x = sum_dpp<0x4E>(x);
-    x = sum_dpp<0x141>(x);
-    x = sum_dpp<0x140>(x);
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 0));
-    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 32));
-    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 48));
-    return upper ? r2 + r3 : r0 + r1;
-}
-
-// acc += A . B on v_mfma_f32_16x16x32_f16, ALWAYS in place (result registers = accumulator input).  Through the builtin hipcc
-// renamed the destination of some MFMAs and put them one slot behind the MFMA that produced their accumulator input; lanes
-// 48..63 of that input were then still being written (a few wrong columns per launch, never the same ones: the result
-// latency of this gfx950 opcode is longer than the hazard tables assume).  In-place chains are interlocked by the hardware;
-// what the compiler no longer sees -- a vector read of a result -- is fenced by mfma_results_ready().
-__device__ __forceinline__ void mfma16(f32x4& acc, const f16x8& a, const f16x8& b) {
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-}
-// first MFMA of a chain: accumulator input = the constant 0 (no vector write of the accumulator in front of the chain)
-__device__ __forceinline__ void mfma16_first(f32x4& acc, const f16x8& a, const f16x8& b) {
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void mfma_results_ready() { asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); }
 
 struct EpiK {
     const float* bias;        // [128] or null
@@ -345,9 +303,9 @@ __global__ __launch_bounds__(64 * (kCons + kProd)) void row_gemm_k384_kernel(con
                 if (RES) v += res[j];
                 if (LN) {
                     if (ep.pre) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rp, goff, j * 512, 0);
-                    const float mu = half_wave_total((v.x + v.y) + (v.z + v.w), upper) * (1.0f / 128.0f);
+                    const float mu = half_wave_total_readlane((v.x + v.y) + (v.z + v.w), upper) * (1.0f / 128.0f);
                     const float4 d = v - f4(mu);
-                    const float var = half_wave_total((d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w), upper) * (1.0f / 128.0f);
+                    const float var = half_wave_total_readlane((d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w), upper) * (1.0f / 128.0f);
                     const float rs = rsqrtf(var + ep.eps);
                     v = fma4(rs * d, gam, bet);
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(mu), rm, soff, j * 4, 0);

@@ -28,6 +28,8 @@
 
 #include <cstdlib>
 #include "row_gemm_n384.h"
+#include "lane_reduce.h"
+#include "f16_scale.h"
 #include "pair.h"
 #include "traversal.h"
 
@@ -40,13 +42,6 @@
 namespace dg {
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kSR = 32;                                  // rows per stage
 constexpr int kPlane = 16 * 512;                         // [k-step 4][k-quarter 4][row 32 (xor-swizzled)][16 B]
 constexpr int kStage = 2 * kPlane + 128;                 // hi, lo, inverse row scales [32]
@@ -57,31 +52,6 @@ constexpr int kOffBitsIn = kOffTab + 2 * 384 * 4;        // ReLU mask words of a
 constexpr int kOffBitsOut = kOffBitsIn + 2 * 2048;       // ... written by the consumers [2][8][64] (with the output tile)
 constexpr int kLds = kOffBitsOut + 2 * 2048;
 constexpr int kCons = 8, kProd = 4, kDepth = 3;
-
-template <int CTRL>
-__device__ __forceinline__ unsigned umax_dpp(unsigned x) {
-    const unsigned moved = static_cast<unsigned>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), CTRL, 0xF, 0xF, true));
-    return x > moved ? x : moved;
-}
-
-// acc += A . B on v_mfma_f32_16x16x32_f16, ALWAYS in place, and the fence in front of the first vector read of a result:
-// see row_gemm_k384.hip (hipcc's renamed destinations one slot behind the producing MFMA read partly written accumulators).
-__device__ __forceinline__ void mfma16(f32x4& acc, const f16x8& a, const f16x8& b) {
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-}
-// first MFMA of a chain: accumulator input = the constant 0 (no vector write of the accumulator in front of the chain)
-__device__ __forceinline__ void mfma16_first(f32x4& acc, const f16x8& a, const f16x8& b) {
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void mfma_results_ready() { asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); }
-
-// packed fp16 pair { fp16(s0 - hi.lo), fp16(s1 - hi.hi) }: the lo plane of two scaled values whose hi plane is `hpk`
-__device__ __forceinline__ unsigned lo_pair(unsigned hpk, float s0, float s1) {
-    unsigned d;
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hpk), "v"(s0));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(d) : "v"(hpk), "v"(s1));
-    return d;
-}
 
 struct Epi {
     const float* bias;            // [384] or null

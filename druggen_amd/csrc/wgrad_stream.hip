@@ -3,7 +3,7 @@
 //     dW[n][k] = sum_r dy[r][n] * x[r][k]        db[n] = sum_r dy[r][n]
 //
 // (reference: `mm(dy.t(), x)` + `sum(dy, 0)` in every Linear backward of src/model/layers.py:50-53,111-116,127,135
-// and inside the gradient penalty's double backward, src/model/loss.py:32-39).  Same arithmetic as SPLIT 2 of
+// and inside the gradient penalty's double backward, src/model/loss.py:32-39).  Same arithmetic as the float32 kernel of
 // linear_wgrad.hip -- fp16 hi + lo operands under one running power-of-two scale per COLUMN of dy and of x, three
 // v_mfma_f32_32x32x16_f16 per product, fp32 accumulation, exact un-scaling at the end -- but every element is
 // converted ONCE per workgroup instead of once per wave that multiplies it (2.5x for the 384-wide shapes; the
@@ -34,6 +34,7 @@
 
 #include <cstdlib>
 #include "wgrad_stream.h"
+#include "f16_scale.h"
 #include "pair.h"
 
 // Developer builds only (-DWS_DBG=<bits>, loaded through DG_LIB; scripts/build_variant.sh): ablations that time the
@@ -51,34 +52,6 @@ namespace dg {
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// 2^(8 - floor(log2 m)) for a finite m > 0 (see linear_wgrad.hip: a column's scale moves again only for a value
-// 64-128 times larger than the one that set it)
-__device__ __forceinline__ float ws_scale_for(float m) {
-    const int e = static_cast<int>((__float_as_uint(m) >> 23) & 255u);
-    int be = 127 + 8 - (e - 127);
-    be = be > 253 ? 253 : (be < 1 ? 1 : be);
-    return __uint_as_float(static_cast<unsigned>(be) << 23);
-}
-__device__ __forceinline__ float ws_pow2_ratio(float num, float den) {      // num <= den, both powers of two
-    const int d = static_cast<int>(__float_as_uint(num) >> 23) - static_cast<int>(__float_as_uint(den) >> 23) + 127;
-    return d < 1 ? 0.f : __uint_as_float(static_cast<unsigned>(d) << 23);
-}
-__device__ __forceinline__ float ws_pow2_inv(float p) { return __uint_as_float((254u - (__float_as_uint(p) >> 23)) << 23); }
-
-// hi = s rounded toward zero to fp16, lo = s - hi (exact in fp32) rounded toward zero, for the pair (v0, v1) * sc
-__device__ __forceinline__ void ws_split2(float v0, float v1, float sc, unsigned& hw, unsigned& lw) {
-    const float s0 = v0 * sc, s1 = v1 * sc;
-    hw = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(s0, s1));
-    float l0, l1;
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(hw), "v"(s0));
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(hw), "v"(s1));
-    lw = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(l0, l1));
-}
-__device__ __forceinline__ float comp4(const float4& v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
-
 constexpr int kConsumers = 8, kProducers = 4, kDepth = 3;
 constexpr int kStageBytes = 32768;                 // one stage of planes: SR rows x (N + K) columns x (hi + lo)
 constexpr int kHdr = 2 * kStageBytes;              // tags [2][4] u32, then ratios [2][N + K], then final inverse scales [N + K]
@@ -323,10 +296,10 @@ __global__ __launch_bounds__(64 * (kConsumers + kProducers)) void wgrad_stream_k
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float a, b2, c2;
-                asm("v_max3_f32 %0, |%1|, |%2|, |%3|" : "=v"(a) : "v"(comp4(set[0], j)), "v"(comp4(set[1], j)), "v"(comp4(set[2], j)));
-                asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(b2) : "v"(a), "v"(comp4(set[3], j)), "v"(comp4(set[4], j)));
-                asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(c2) : "v"(b2), "v"(comp4(set[5], j)), "v"(comp4(set[6], j)));
-                asm("v_max_f32_e64 %0, %1, |%2|" : "=v"(m[j]) : "v"(c2), "v"(comp4(set[7], j)));
+                asm("v_max3_f32 %0, |%1|, |%2|, |%3|" : "=v"(a) : "v"(comp(set[0], j)), "v"(comp(set[1], j)), "v"(comp(set[2], j)));
+                asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(b2) : "v"(a), "v"(comp(set[3], j)), "v"(comp(set[4], j)));
+                asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(c2) : "v"(b2), "v"(comp(set[5], j)), "v"(comp(set[6], j)));
+                asm("v_max_f32_e64 %0, %1, |%2|" : "=v"(m[j]) : "v"(c2), "v"(comp(set[7], j)));
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -341,8 +314,8 @@ __global__ __launch_bounds__(64 * (kConsumers + kProducers)) void wgrad_stream_k
                 float rp[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const float nsc = m[j] * sc[j] >= 32768.f ? ws_scale_for(m[j]) : sc[j];
-                    rp[j] = ws_pow2_ratio(nsc, sc[j]);
+                    const float nsc = m[j] * sc[j] >= 32768.f ? scale_for(m[j]) : sc[j];
+                    rp[j] = pow2_ratio(nsc, sc[j]);
                     sc[j] = nsc;
                 }
                 if (rg == 0) st4(ratios + (t & 1) * COLS + p * CW + 4 * cq, make_float4(rp[0], rp[1], rp[2], rp[3]));
@@ -357,10 +330,10 @@ __global__ __launch_bounds__(64 * (kConsumers + kProducers)) void wgrad_stream_k
                 for (int pr = 0; pr < 4; ++pr) {
                     unsigned h, l;
                     if (WS_DBG & 2) {
-                        h = __float_as_uint(comp4(set[2 * pr], j));
-                        l = __float_as_uint(comp4(set[2 * pr + 1], j));
+                        h = __float_as_uint(comp(set[2 * pr], j));
+                        l = __float_as_uint(comp(set[2 * pr + 1], j));
                     } else {
-                        ws_split2(comp4(set[2 * pr], j), comp4(set[2 * pr + 1], j), sc[j], h, l);
+                        split2_f16(comp(set[2 * pr], j), comp(set[2 * pr + 1], j), sc[j], h, l);
                     }
                     hw[pr] = h;
                     lw[pr] = l;
@@ -397,7 +370,7 @@ __global__ __launch_bounds__(64 * (kConsumers + kProducers)) void wgrad_stream_k
         }
         // final inverse scales for the consumers' un-scaling; column sums of dy
         if (rg == 0) {
-            float4 inv = make_float4(ws_pow2_inv(sc[0]), ws_pow2_inv(sc[1]), ws_pow2_inv(sc[2]), ws_pow2_inv(sc[3]));
+            float4 inv = make_float4(pow2_inv(sc[0]), pow2_inv(sc[1]), pow2_inv(sc[2]), pow2_inv(sc[3]));
             st4(fin + p * CW + 4 * cq, inv);
         }
         __syncthreads();
