@@ -2,10 +2,6 @@
 attention half of an Encoder_Block as one autograd node (float32: dg_attn_half_f32_*; bf16: dg_attn_half_*)."""
 from __future__ import annotations
 
-import contextlib
-import ctypes
-import threading
-
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -99,12 +95,26 @@ def _core_bwd2(q, k, v, e, ws, wo, tq, tk, tv, te, gq, gk, gv, ge, gws, gwo, alp
     _account("attn_bwd2", base + 2 * extra, floor=base)
 
 
+def _attn_bwd_launch(q, k, v, e, ws, wo, alpha, add_e=None):
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
+    de = torch.empty_like(e)
+    _core_bwd(q, k, v, e, ws, wo, add_e, dq, dk, dv, de, alpha)
+    return dq, dk, dv, de
+
+
+def _attn_bwd2_launch(q, k, v, e, ws, wo, tq, tk, tv, te, alpha):
+    gq, gk, gv, gwo = (torch.empty_like(q) for _ in range(4))
+    ge = torch.empty_like(e)
+    gws = torch.empty_like(e) if ws is not None else None
+    _core_bwd2(q, k, v, e, ws, wo, tq, tk, tv, te, gq, gk, gv, ge, gws, gwo, alpha)
+    return gq, gk, gv, ge, gws, gwo
+
+
 class _AttnCore(Function):
     @staticmethod
     def forward(ctx, q, k, v, e, alpha, need_s):
         q, k, v, e = _c(q), _c(k), _c(v), _c(e)
         B, N, C = _attn_shapes(q, e)
-        _check_neighbours(N)
         s = torch.empty_like(e) if need_s else None
         o = torch.empty_like(q)
         _core_fwd(q, k, v, e, s, o, alpha, B, N, C)
@@ -123,35 +133,23 @@ class _AttnCore(Function):
             wo = torch.zeros_like(q)
         if ws is not None and ws.numel() == 0:
             ws = None
-        dq, dk, dv, de = _AttnCoreBwd.apply(q, k, v, e, ws, wo, ctx.alpha)
-        return dq, dk, dv, de, None, None
+        return (*_AttnCoreBwd.apply(q, k, v, e, ws, wo, ctx.alpha), None, None)
 
 
 class _AttnCoreBwd(Function):
     @staticmethod
     def forward(ctx, q, k, v, e, ws, wo, alpha):
-        B, N, C = _attn_shapes(q, e)
-        ws = None if ws is None else _c(ws)
-        wo = _c(wo)
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
-        de = torch.empty_like(e)
-        _core_bwd(q, k, v, e, ws, wo, None, dq, dk, dv, de, alpha)
+        _attn_shapes(q, e)
+        ws, wo = (None if ws is None else _c(ws)), _c(wo)
         ctx.save_for_backward(q, k, v, e, ws, wo)
         ctx.alpha = alpha
-        return dq, dk, dv, de
+        return _attn_bwd_launch(q, k, v, e, ws, wo, alpha)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, tq, tk, tv, te):
         q, k, v, e, ws, wo = ctx.saved_tensors
-        B, N, C = _attn_shapes(q, e)
-        tq, tk, tv, te = _c(tq), _c(tk), _c(tv), _c(te)
-        gq, gk, gv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
-        ge = torch.empty_like(e)
-        gws = torch.empty_like(e) if ws is not None else None
-        gwo = torch.empty_like(q)
-        _core_bwd2(q, k, v, e, ws, wo, tq, tk, tv, te, gq, gk, gv, ge, gws, gwo, ctx.alpha)
-        return gq, gk, gv, ge, gws, gwo, None
+        return (*_attn_bwd2_launch(q, k, v, e, ws, wo, _c(tq), _c(tk), _c(tv), _c(te), ctx.alpha), None)
 
 
 def attn_core(q, k, v, e, alpha: float, need_s: bool = True):
@@ -197,6 +195,184 @@ def attn_half_f32_bwd1_supported(dy2f, B: int, N: int, C: int, graph: bool = Fal
             and (B >= 128 or mode == "force") and (not graph or mode != "nograph"))
 
 
+# The block nodes' inputs, outputs and saved tensors by name: each tuple is the positional order of one ``forward`` (held against
+# the signatures by tests/test_attention_spec_host.py), and every position the nodes need -- a needs_input_grad look-up, the slot
+# of a gradient in a ``backward`` return, a saved tensor -- is derived from them (``_by_name``, ``dict(zip(names, ...))``).
+_ATTN_LINEAR = ("wq", "bq", "wk", "bk", "wv", "bv", "we", "be", "woe", "boe", "won", "bon")
+_ATTN_AFFINE = ("g3", "b3", "g4", "b4")      # ln3 / ln4 affine parameters
+_ATTN_TENSORS = ("x1", "y") + _ATTN_LINEAR + _ATTN_AFFINE
+# the parameters that leave the penalty's forward as alias outputs (see _weight_alias), in the order of those outputs
+_ATTN_ALIASES = ("wq", "wk", "wv", "we", "woe", "won", "g3", "g4")
+_ATTN_ADJOINTS = ("add3", "add4", "aq", "ak", "av", "ae")      # what the second order hands back to the forward node
+
+
+def _by_name(names, values):
+    """A node's positional inputs, or a ``backward`` return, from {name: value}: one slot per declared name, None where the
+    mapping is silent; a name that is not declared raises."""
+    unknown = [n for n in values if n not in names]
+    if unknown:
+        raise KeyError(f"{unknown} not among {names}")
+    return tuple(values.get(n) for n in names)
+
+
+# The node side of the block (R = B N rows), shared by the float32 / unfused nodes, their second order and the fused bf16 node
+def _qkv_fwd(x2, ws, bs):
+    """q, k, v of the rows ``x2`` (``bs`` entries may be None): one launch where ``lin3_supported``, else three row GEMMs."""
+    if lin3_supported(x2, ws):
+        return lin3(x2, ws, bs)
+    C = x2.shape[1]
+    return [row_gemm(x2, packed_weight(w, 0, x2.dtype), C, C, bias=b) for w, b in zip(ws, bs)]
+
+
+def _qkv_bwd_input(dqkv, ws, residual):
+    """residual + dq Wq + dk Wk + dv Wv: one launch where ``lin3_supported``, else three row GEMMs, each adding in its epilogue."""
+    if lin3_supported(dqkv[0], ws):
+        return sum3(*dqkv, ws, residual=residual)
+    C = residual.shape[1]
+    for d, w in zip(dqkv, ws):
+        residual = row_gemm(d, packed_weight(w, 1, d.dtype), C, C, residual=residual)
+    return residual
+
+
+def _attn_wgrads(ws, dqkv, x2, e, out_n, out_e, want_bias, open_batch=True):
+    """{input name: gradient} of the block's projections from ONE ``_wgrad_many`` call.  q, k, v: ``dqkv`` against their shared
+    input rows ``x2``, one stacked [384,128] item where ``lin3_supported``, else three.  ``e`` / ``out_n`` / ``out_e``: (output
+    gradient rows, input rows), or None for a projection the caller leaves out.  ``want_bias``: the first-order form (second
+    order: weights only)."""
+    stacked = lin3_supported(dqkv[0], ws)
+    items = [(tuple(dqkv), x2, want_bias)] if stacked else [(d, x2, want_bias) for d in dqkv]
+    rest = [(n, p) for n, p in (("e", e), ("on", out_n), ("oe", out_e)) if p is not None]
+    items += [(dy, x, want_bias) for _, (dy, x) in rest]
+    # (out_n's weight gradient over the node rows rides in out_e's over the edge rows)
+    res = _wgrad_many(items, open_batch=open_batch, pair_from=len(items) - 2 if out_e is not None else None)
+    if stacked:      # rows 0..127 / 128..255 / 256..383 of the stacked gradient
+        (w3, b3), *res = res
+        res = [(w3[r:r + 128], None if b3 is None else b3[r:r + 128]) for r in (0, 128, 256)] + res
+    out = {}
+    for n, (dw, db) in zip(["q", "k", "v"] + [n for n, _ in rest], res):
+        out["w" + n], out["b" + n] = dw, db
+    return out
+
+
+def _ln3_bwd_do(pre3, g3, mean3, rstd3, dx2f, add3, won, want_aff, inb):
+    """(dz3, dgamma3, dbeta3, do): ln3's backward, then the out_n input gradient do = dz3 Won."""
+    dz3, dg3, db3 = _ln_bwd_rows(pre3, g3, mean3, rstd3, dx2f, add3, want_affine=want_aff, batch_slot=0 if inb else None)
+    C = dz3.shape[1]
+    return dz3, dg3, db3, row_gemm(dz3, packed_weight(won, 1, dz3.dtype), C, C)
+
+
+# The fused launches of the edge side: tensors in, outputs allocated, one native call, one ``_account``
+def _half_f32_fwd(yf, q, k, v, we, be, woe, boe, g4, b4, B, N, C, alpha, eps4, keep):
+    """e projection, scores, softmax / node output, out_e, residual, ln4: one launch (dg_attn_half_f32_fwd); e, s and the
+    pre-LayerNorm sum are written for the backward only (``keep``).  Returns (e, s, o, y2, pre4, mean4, rstd4)."""
+    lib, P, F = _lib.load(), _lib.ptr, _lib.fptr
+    R = yf.shape[0]
+    e, s, pre4 = (torch.empty_like(yf) if keep else None for _ in range(3))
+    o, y2 = torch.empty_like(q), torch.empty_like(yf)
+    mean4, rstd4 = (torch.empty(R, dtype=torch.float32, device=yf.device) for _ in range(2))
+    with _dev(q):
+        _lib.check(lib.dg_attn_half_f32_fwd(P(yf), P(q), P(k), P(v), packed_weight(we, 0, yf.dtype).data_ptr(), F(_c(be)),
+                                            packed_weight(woe, 0, yf.dtype).data_ptr(), F(_c(boe)), F(_c(g4)), F(_c(b4)), P(e), P(s),
+                                            P(o), P(y2), P(pre4), P(mean4), P(rstd4), B, N, C, alpha, eps4, _lib.stream_of(q)),
+                   "dg_attn_half_f32_fwd")
+    _account("attn_half_fwd", 4 * (R * C * (5 if keep else 2) + 4 * B * N * C), 4 * R * C * C,
+             floor=4 * (R * C * 2 + 4 * B * N * C))
+    return e, s, o, y2, pre4, mean4, rstd4
+
+
+def _half_f32_bwd1(dy2f, pre4, mean4, rstd4, g4, woe, ev, qv, kv, vv, do, alpha, want_aff, keep_ds, inb):
+    """ln4 backward + ds = dz4 Woe + the attention core's backward: one launch (dg_attn_half_f32_bwd1); ds stays on chip
+    unless ``keep_ds``.  Returns (dz4, ds, dq, dk, dv, de, dgamma4, dbeta4)."""
+    lib, P = _lib.load(), _lib.ptr
+    B, N, C = qv.shape
+    dev, adt = dy2f.device, dy2f.dtype
+    dz4, de = torch.empty_like(dy2f), torch.empty_like(dy2f)
+    ds = torch.empty_like(dy2f).view(B, N, N, C) if keep_ds else None
+    dq, dk, dv = (torch.empty(B, N, C, dtype=adt, device=dev) for _ in range(3))
+    dg4, db4 = (torch.empty(2, C, dtype=torch.float32, device=dev).unbind(0) if want_aff else (None, None))
+    with _dev(dy2f):
+        ws = _scratch(dy2f, int(lib.dg_attn_half_f32_bwd1_workspace_bytes(B)), "ahb_batch" if inb else "ahb")
+        woe_t = packed_weight(woe, 1, adt).data_ptr()
+        _lib.check(lib.dg_attn_half_f32_bwd1(P(dy2f), P(pre4), P(mean4), P(rstd4), _lib.fptr(_c(g4)), woe_t, P(ev), P(qv), P(kv), P(vv),
+                                             P(do), P(dz4), P(ds), P(de), P(dq), P(dk), P(dv), P(dg4), P(db4), ws.data_ptr(), ws.numel(),
+                                             B, N, C, alpha, _lib.stream_of(dy2f)), "dg_attn_half_f32_bwd1")
+    _account("attn_half_bwd", 4 * (dy2f.shape[0] * C * (5 if ds is None else 6) + 7 * B * N * C), 2 * dy2f.shape[0] * C * C)
+    return dz4, ds, dq, dk, dv, de.view(B, N, N, C), dg4, db4
+
+
+_half_pack_cache = PackCache(1024)
+
+
+def _attn_half_packed(we, woe, dtype):
+    """Fragment-order copies of (e.weight, out_e.weight) and their transposes for the fused attention-half kernels
+    (dg_attn_half_pack), cached like ``packed_weight``."""
+    def make(we, woe):
+        lib = _lib.load()
+        code = _lib.DTYPES[dtype]
+        packed = torch.empty(int(lib.dg_attn_half_packed_bytes(code)), dtype=torch.uint8, device=we.device)
+        with _dev(we):
+            _lib.check(lib.dg_attn_half_pack(_lib.fptr(_c(we.detach())), _lib.fptr(_c(woe.detach())), packed.data_ptr(), code,
+                                             _lib.stream_of(we)), "dg_attn_half_pack")
+        return packed
+    return _half_pack_cache.get((we, woe), (dtype,), make)
+
+
+def _half_fwd(yc, q, k, v, we, be, woe, boe, g4, b4, B, N, C, alpha, eps4, need_edge):
+    """The whole edge side of the block in one launch (dg_attn_half_fwd): e and s never exist in HBM.  Returns
+    (o, y2, pre4, mean4, rstd4); the last four are None without ``need_edge``."""
+    lib, P, F = _lib.load(), _lib.ptr, _lib.fptr
+    o = torch.empty_like(q)
+    y2, pre4 = (torch.empty_like(yc) if need_edge else None for _ in range(2))
+    mean4, rstd4 = (torch.empty(B * N * N, dtype=torch.float32, device=q.device) if need_edge else None for _ in range(2))
+    packed = _attn_half_packed(we, woe, q.dtype)
+    with _dev(q):
+        _lib.check(lib.dg_attn_half_fwd(P(yc), P(q), P(k), P(v), packed.data_ptr(), F(_c(be)), F(_c(boe)), F(_c(g4)), F(_c(b4)), P(o),
+                                        P(y2), P(pre4), P(mean4), P(rstd4), B, N, C, alpha, eps4, _lib.dt(q), _lib.stream_of(q)),
+                   "dg_attn_half_fwd")
+    es = q.element_size()
+    _account("attn_half_fwd", es * B * ((3 if need_edge else 1) * N * N * C + 4 * N * C),
+             2 * B * N * N * C * C * (2 if need_edge else 1), floor=es * B * ((2 if need_edge else 1) * N * N * C + 4 * N * C))
+    return o, y2, pre4, mean4, rstd4
+
+
+def _half_bwd(y, dz4, q, k, v, do, we, be, woe, B, N, C, alpha, wants_w, need_edge):
+    """The edge side's backward in one launch (dg_attn_half_bwd): e and s are recomputed from ``y``.  Returns (dy, dq, dk, dv,
+    dwe, dbe, dwoe, dboe); the weight gradients, made inside the kernel, are None unless ``wants_w`` (out_e's: and ``need_edge``)."""
+    lib, P = _lib.load(), _lib.ptr
+    dy = torch.empty_like(y)
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
+    dwe = dbe = dwoe = dboe = None
+    if wants_w:
+        dwe, dbe = torch.empty_like(we), torch.empty(C, dtype=torch.float32, device=q.device)
+    if wants_w and need_edge:
+        dwoe, dboe = torch.empty_like(woe), torch.empty(C, dtype=torch.float32, device=q.device)
+    with _dev(q):
+        ws = _scratch(q, int(lib.dg_attn_half_bwd_workspace_bytes(B, N)), "half")
+        _lib.check(lib.dg_attn_half_bwd(P(y), P(dz4), P(q), P(k), P(v), P(do), _attn_half_packed(we, woe, q.dtype).data_ptr(),
+                                        _lib.fptr(_c(be)), P(dy), P(dq), P(dk), P(dv), P(dwe), P(dbe), P(dwoe), P(dboe), ws.data_ptr(),
+                                        ws.numel(), B, N, C, alpha, _lib.dt(q), _lib.stream_of(q)), "dg_attn_half_bwd")
+    es = q.element_size()
+    _account("attn_half_bwd", es * B * ((3 if need_edge else 2) * N * N * C + 8 * N * C),
+             2 * B * N * N * C * C * ((3 if need_edge else 2) + (2 if wants_w and need_edge else (1 if wants_w else 0))))
+    return dy, dq, dk, dv, dwe, dbe, dwoe, dboe
+
+
+_LN_HANDLE = ("ppre", "pmean", "prstd", "pgamma", "pbeta")
+_ATTN_IN = _ATTN_TENSORS + ("alpha", "eps3", "eps4", "need_edge") + _LN_HANDLE      # _AttnBlock.forward
+# _AttnBlock.forward's outputs = the gradients its backward receives: with / without the edge output, then the aliases
+_ATTN_OUT_EDGE = ("x2", "y2", "pre3", "pre4", "q", "k", "v", "e")
+_ATTN_OUT_NODE = ("x2", "pre3", "q", "k", "v", "e")
+# what _AttnBlock saves: always; when need_edge; when an LNHandle came in
+_ATTN_SAVED = ("x1", "y") + _ATTN_ALIASES + ("q", "k", "v", "e", "s", "o", "mean3", "rstd3", "pre3")
+_ATTN_SAVED_EDGE = ("mean4", "rstd4", "pre4")
+_ATTN_SAVED_PREV = ("ppre", "pmean", "prstd", "pgamma")
+
+
+def _attn_saved(need_edge, has_prev):
+    """Names of the tensors ``_AttnBlock`` saves, in saved order."""
+    return _ATTN_SAVED + (_ATTN_SAVED_EDGE if need_edge else ()) + (_ATTN_SAVED_PREV if has_prev else ())
+
+
 class _AttnBlock(Function):
     """x2 = LN3(x1 + out_n(o)), y2 = LN4(y + out_e(s)) with (s, o) = attention(q(x1), k(x1), v(x1), e(y))
     -- reference layers.py:111-135 + 186-190 -- as ONE autograd node: every projection is a row-GEMM
@@ -214,131 +390,85 @@ class _AttnBlock(Function):
         x1f, yf = _c(x1).reshape(-1, C), _c(y).reshape(-1, C)
         adt = x1f.dtype
         pw = lambda w_, m_: packed_weight(w_, m_, adt)
-        if lin3_supported(x1f, (wq, wk, wv)):      # q, k, v share their input: one launch
-            q, k, v = lin3(x1f, (wq, wk, wv), (bq, bk, bv))
-        else:
-            q = row_gemm(x1f, pw(wq, 0), C, C, bias=bq)
-            k = row_gemm(x1f, pw(wk, 0), C, C, bias=bk)
-            v = row_gemm(x1f, pw(wv, 0), C, C, bias=bv)
-        lib = _lib.load()
+        q, k, v = _qkv_fwd(x1f, (wq, wk, wv), (bq, bk, bv))
         # no input needs a gradient (the Generator's forward inside the D step): the pre-LayerNorm sums are not written
         keep = any(ctx.needs_input_grad)
-        o = torch.empty_like(q)
+        y2 = mean4 = rstd4 = pre4 = None
         fused_edge = need_edge and attn_half_f32_supported(yf, N, C)
         if fused_edge:
-            # e projection, scores, softmax / node output, out_e, residual, ln4: one launch (dg_attn_half_f32_fwd); e, s and
-            # the pre-LayerNorm sum are written for the backward only
-            R = yf.shape[0]
-            dev = yf.device
-            e = torch.empty(R, C, dtype=adt, device=dev) if keep else None
-            s = torch.empty(R, C, dtype=adt, device=dev) if keep else None
-            y2 = torch.empty(R, C, dtype=adt, device=dev)
-            pre4 = torch.empty(R, C, dtype=adt, device=dev) if keep else None
-            mean4 = torch.empty(R, dtype=torch.float32, device=dev)
-            rstd4 = torch.empty(R, dtype=torch.float32, device=dev)
-            with _dev(q):
-                _lib.check(lib.dg_attn_half_f32_fwd(_lib.ptr(yf), _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), pw(we, 0).data_ptr(),
-                                                    _lib.fptr(_c(be)), pw(woe, 0).data_ptr(), _lib.fptr(_c(boe)), _lib.fptr(_c(g4)),
-                                                    _lib.fptr(_c(b4)), _lib.ptr(e), _lib.ptr(s), _lib.ptr(o), _lib.ptr(y2),
-                                                    _lib.ptr(pre4), _lib.ptr(mean4), _lib.ptr(rstd4), B, N, C, alpha, eps4,
-                                                    _lib.stream_of(q)), "dg_attn_half_f32_fwd")
-            _account("attn_half_fwd", 4 * (R * C * (5 if keep else 2) + 4 * B * N * C), 4 * R * C * C,
-                     floor=4 * (R * C * 2 + 4 * B * N * C))
+            e, s, o, y2, pre4, mean4, rstd4 = _half_f32_fwd(yf, q, k, v, we, be, woe, boe, g4, b4, B, N, C, alpha, eps4, keep)
         else:
             e = row_gemm(yf, pw(we, 0), C, C, bias=be)
             s = torch.empty_like(e) if need_edge else None
+            o = torch.empty_like(q)
             _core_fwd(q, k, v, e, s, o, alpha, B, N, C)
         r3 = row_gemm(o, pw(won, 0), C, C, bias=bon, residual=x1f, ln=(_c(g3), _c(b3), eps3), want_pre=keep)
         x2, mean3, rstd3, pre3 = r3 if keep else (*r3, None)
-        outs = [x2.view(B, N, C)]
-        # the penalty's forward: the parameters leave as alias outputs (see _weight_alias)
+        if need_edge and not fused_edge:
+            r4 = row_gemm(s, pw(woe, 0), C, C, bias=boe, residual=yf, ln=(_c(g4), _c(b4), eps4), want_pre=keep)
+            y2, mean4, rstd4, pre4 = r4 if keep else (*r4, None)
+        have = dict(x1=x1, y=y, wq=wq, wk=wk, wv=wv, we=we, woe=woe, won=won, g3=g3, g4=g4, q=q, k=k, v=v, e=e, s=s, o=o,
+                    mean3=mean3, rstd3=rstd3, pre3=pre3, mean4=mean4, rstd4=rstd4, pre4=pre4,
+                    ppre=ppre, pmean=pmean, prstd=prstd, pgamma=pgamma)
+        # the penalty's forward: the parameters leave as alias outputs, and the aliases are what is saved (see _weight_alias)
         ctx.alias = bool(keep and in_second_order_forward() and _alias_outputs_enabled())
-        aliases = ()
         if ctx.alias:
-            aliases = tuple(_weight_alias(t) for t in (wq, wk, wv, we, woe, won, g3, g4))
-            wq, wk, wv, we, woe, won, g3, g4 = aliases
-        saved = [x1, y, wq, wk, wv, we, woe, won, g3, g4, q, k, v, e, s, o, mean3, rstd3, pre3]
-        if need_edge:
-            if not fused_edge:
-                r4 = row_gemm(s, pw(woe, 0), C, C, bias=boe, residual=yf, ln=(_c(g4), _c(b4), eps4), want_pre=keep)
-                y2, mean4, rstd4, pre4 = r4 if keep else (*r4, None)
-            outs.append(y2.view(B, N, N, C))
-            saved += [mean4, rstd4, pre4]
-        else:
-            pre4 = None
+            have.update({n: _weight_alias(have[n]) for n in _ATTN_ALIASES})
         ctx.has_prev = ppre is not None
-        if ctx.has_prev:
-            saved += [ppre, pmean, prstd, pgamma]
-        ctx.save_for_backward(*saved)
+        ctx.save_for_backward(*(have[n] for n in _attn_saved(need_edge, ctx.has_prev)))
         ctx.cfg = (alpha, eps3, eps4, need_edge, (B, N, C))
         ctx.extra = (bq, bk, bv, be, boe, bon, b3, b4)
         ctx.set_materialize_grads(False)
         # pre3 / pre4 / q / k / v / e are outputs only so that the second order of the gradient penalty
         # can return their adjoints to THIS node, where they join the first-order gradients inside one
         # backward pass (see _AttnBlockBwd.backward); module code never sees them.
-        return tuple(outs) + ((pre3, pre4) if need_edge else (pre3,)) + (q, k, v, e) + aliases
+        have.update(x2=x2.view(B, N, C), y2=y2.view(B, N, N, C) if need_edge else None)
+        return tuple(have[n] for n in (_ATTN_OUT_EDGE if need_edge else _ATTN_OUT_NODE) + (_ATTN_ALIASES if ctx.alias else ()))
 
     @staticmethod
-    def backward(ctx, dx2, *more):
+    def backward(ctx, *gouts):
         alpha, eps3, eps4, need_edge, (B, N, C) = ctx.cfg
-        galias = ()
-        if ctx.alias:      # second-order gradients of wq, wk, wv, we, woe, won, g3, g4 (or None each)
-            more, galias = more[:-8], more[-8:]
-        sv = ctx.saved_tensors
-        x1, y, wq, wk, wv, we, woe, won, g3, g4, q, k, v, e, s, o, mean3, rstd3, pre3 = sv[:19]
-        mean4, rstd4, pre4 = sv[19:22] if need_edge else (None, None, None)
+        # gradients of the outputs by output name; the aliases' are the second-order gradients of the parameters (or None each)
+        g = dict(zip((_ATTN_OUT_EDGE if need_edge else _ATTN_OUT_NODE) + (_ATTN_ALIASES if ctx.alias else ()), gouts))
+        sv = dict(zip(_attn_saved(need_edge, ctx.has_prev), ctx.saved_tensors))
         bq, bk, bv, be, boe, bon, b3, b4 = ctx.extra
-        if need_edge:
-            dy2, add3, add4, aq, ak, av, ae = more
-            if dy2 is None:
-                dy2 = torch.zeros_like(pre4)
-        else:
-            dy2 = add4 = None
-            add3, aq, ak, av, ae = more
-        if dx2 is None:
-            dx2 = torch.zeros_like(pre3)
-        wants_w = ctx.needs_input_grad[2] and not _inputs_only()
-        want_aff = any(ctx.needs_input_grad[14:18]) and not _inputs_only()      # ln3 / ln4 affine parameters
-        ppre = pmean = prstd = pgamma = None
-        if ctx.has_prev:
-            ppre, pmean, prstd, pgamma = sv[-4:]
+        needs = dict(zip(_ATTN_IN, ctx.needs_input_grad))
+        dx2 = g["x2"] if g["x2"] is not None else torch.zeros_like(sv["pre3"])
+        dy2 = g.get("y2")
+        if need_edge and dy2 is None:
+            dy2 = torch.zeros_like(sv["pre4"])
+        adjoints = dict(add3=g["pre3"], add4=g.get("pre4"), aq=g["q"], ak=g["k"], av=g["v"], ae=g["e"])
+        wants_w = needs["wq"] and not _inputs_only()
+        want_aff = any(needs[n] for n in _ATTN_AFFINE) and not _inputs_only()
         # y is the output of a LayerNorm whose handle came with it, and no graph is being recorded: that LayerNorm's
         # backward runs as the epilogue of the dy GEMM (its result is the gradient of `ppre`, y itself gets none)
         # (not in the last pass of a double backward -- recognisable by the adjoints of this node's extra outputs: there
         # the producing feed-forward node's `pre` ALSO receives the second-order adjoint, and autograd would join the
         # two with an edge-level add that costs more than the fused LayerNorm backward saves)
-        second_pass = any(t is not None for t in (add3, add4, aq, ak, av, ae))
-        fuse_prev = bool(ctx.has_prev and not torch.is_grad_enabled() and not second_pass and ctx.needs_input_grad[1]
-                         and ctx.needs_input_grad[22] and row_gemm_ln_bwd_supported(q, C)
-                         and tuple(ppre.shape) == (B * N * N, C))
-        outs = _AttnBlockBwd.apply(x1, y, wq, bq, wk, bk, wv, bv, we, be, woe, boe, won, bon, g3, g4,
-                                   q, k, v, e, s, o, mean3, rstd3, pre3, mean4, rstd4, pre4, dx2, dy2,
-                                   add3, add4, aq, ak, av, ae,
-                                   alpha, need_edge, ctx.needs_input_grad[0], ctx.needs_input_grad[1], wants_w,
-                                   ppre if fuse_prev else None, pmean, prstd, pgamma, want_aff,
-                                   not torch.is_grad_enabled())      # (no graph is being recorded: see _AttnBlockBwd)
-        (dx1, dy, dwq, dbq, dwk, dbk, dwv, dbv, dwe, dbe, dwoe, dboe, dwon, dbon, dg3, db3, dg4, db4, dzp, dgp, dbp) = outs
-        if any(g is not None for g in galias):
-            dwq, dwk, dwv, dwe, dwoe, dwon, dg3, dg4 = _join_alias_grads((dwq, dwk, dwv, dwe, dwoe, dwon, dg3, dg4), galias)
-        if not (ctx.needs_input_grad[25] and not _inputs_only()):
-            dgp = dbp = None
-        return (dx1, dy, dwq, dbq, dwk, dbk, dwv, dbv, dwe, dbe, dwoe, dboe, dwon, dbon, dg3, db3, dg4, db4,
-                None, None, None, None, dzp, None, None, dgp, dbp)
+        second_pass = any(t is not None for t in adjoints.values())
+        fuse_prev = bool(ctx.has_prev and not torch.is_grad_enabled() and not second_pass and needs["y"]
+                         and needs["ppre"] and row_gemm_ln_bwd_supported(sv["q"], C)
+                         and tuple(sv["ppre"].shape) == (B * N * N, C))
+        ins = dict(sv, **adjoints, bq=bq, bk=bk, bv=bv, be=be, boe=boe, bon=bon, dx2=dx2, dy2=dy2, alpha=alpha,
+                   need_edge=need_edge, want_x=needs["x1"], want_y=needs["y"], wants_w=wants_w, want_aff=want_aff,
+                   no_graph=not torch.is_grad_enabled())      # (no graph is being recorded: see _AttnBlockBwd)
+        if not fuse_prev:
+            ins["ppre"] = None
+        outs = _AttnBlockBwd.apply(*_by_name(_ATTN_BWD_IN, ins))
+        grads = dict(zip(_ATTN_BWD_OUT, outs))
+        galias = [g.get(n) for n in _ATTN_ALIASES]
+        if any(t is not None for t in galias):
+            grads.update(zip(_ATTN_ALIASES, _join_alias_grads([grads[n] for n in _ATTN_ALIASES], galias)))
+        if not (needs["pgamma"] and not _inputs_only()):
+            grads["pgamma"] = grads["pbeta"] = None
+        return _by_name(_ATTN_IN, grads)
 
 
-def _attn_bwd_launch(q, k, v, e, ws, wo, alpha, add_e=None):
-    dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
-    de = torch.empty_like(e)
-    _core_bwd(q, k, v, e, ws, wo, add_e, dq, dk, dv, de, alpha)
-    return dq, dk, dv, de
-
-
-def _attn_bwd2_launch(q, k, v, e, ws, wo, tq, tk, tv, te, alpha):
-    gq, gk, gv, gwo = (torch.empty_like(q) for _ in range(4))
-    ge = torch.empty_like(e)
-    gws = torch.empty_like(e) if ws is not None else None
-    _core_bwd2(q, k, v, e, ws, wo, tq, tk, tv, te, gq, gk, gv, ge, gws, gwo, alpha)
-    return gq, gk, gv, ge, gws, gwo
+# _AttnBlockBwd.forward's inputs, and its outputs: the gradients of these inputs of _AttnBlock.forward
+_ATTN_BWD_IN = (("x1", "y") + _ATTN_LINEAR + ("g3", "g4", "q", "k", "v", "e", "s", "o", "mean3", "rstd3", "pre3", "mean4", "rstd4",
+                                              "pre4", "dx2", "dy2") + _ATTN_ADJOINTS
+                + ("alpha", "need_edge", "want_x", "want_y", "wants_w", "ppre", "pmean", "prstd", "pgamma", "want_aff", "no_graph"))
+_ATTN_BWD_OUT = _ATTN_TENSORS + ("ppre", "pgamma", "pbeta")
 
 
 class _AttnBlockBwd(Function):
@@ -353,8 +483,9 @@ class _AttnBlockBwd(Function):
     @staticmethod
     def forward(ctx, *args):
         # one reduce launch for the block: six weight gradients + two LayerNorms' dgamma / dbeta
-        wants_w = args[40] or (len(args) > 45 and args[45])      # weight gradients or LayerNorm affine gradients
-        with _reduce_batch(args[0], on=bool(wants_w)) as inb:
+        named = dict(zip(_ATTN_BWD_IN, args))
+        wants_w = named["wants_w"] or named.get("want_aff")      # weight gradients or LayerNorm affine gradients
+        with _reduce_batch(named["x1"], on=bool(wants_w)) as inb:
             return _AttnBlockBwd._forward(ctx, inb, *args)
 
     @staticmethod
@@ -371,9 +502,8 @@ class _AttnBlockBwd(Function):
         x1f, yf = _c(x1).reshape(-1, C), _c(y).reshape(-1, C)
         dx2f = _c(cast(dx2)).reshape(-1, C)
         cadd = lambda t: None if t is None else _c(cast(t)).reshape(-1, C)
-        dz3, dg3, db3 = _ln_bwd_rows(pre3, g3, mean3, rstd3, dx2f, cadd(add3), want_affine=want_aff,
-                                     batch_slot=0 if inb else None)
-        do = row_gemm(dz3, pw(won, 1), C, C).view(B, N, C)
+        dz3, dg3, db3, do = _ln3_bwd_do(pre3, g3, mean3, rstd3, dx2f, cadd(add3), won, want_aff, inb)
+        do = do.view(B, N, C)
         ds = dz4 = dg4 = db4 = dy2f = None
         qv, kv, vv, ev = q.view(B, N, C), k.view(B, N, C), v.view(B, N, C), e.view(B, N, N, C)
         fused1 = None
@@ -381,25 +511,10 @@ class _AttnBlockBwd(Function):
             dy2f = _c(cast(dy2)).reshape(-1, C)
             if (add4 is None and all(t is None for t in (aq, ak, av, ae))
                     and attn_half_f32_bwd1_supported(dy2f, B, N, C, graph=not no_graph)):
-                # ln4 backward + ds = dz4 Woe + the attention core's backward: one launch; ds stays on chip unless a graph is
-                # being recorded (the penalty's first backward: its second order reads ds)
-                lib = _lib.load()
-                dev = dy2f.device
-                dz4, de = torch.empty_like(dy2f), torch.empty_like(dy2f)
-                ds = None if no_graph else torch.empty_like(dy2f).view(B, N, N, C)
-                dq, dk, dv = (torch.empty(B, N, C, dtype=adt, device=dev) for _ in range(3))
-                dg4, db4 = (torch.empty(2, C, dtype=torch.float32, device=dev).unbind(0) if want_aff else (None, None))
-                with _dev(dy2f):
-                    ws = _scratch(dy2f, int(lib.dg_attn_half_f32_bwd1_workspace_bytes(B)), "ahb_batch" if inb else "ahb")
-                    _lib.check(lib.dg_attn_half_f32_bwd1(_lib.ptr(dy2f), _lib.ptr(pre4), _lib.ptr(mean4), _lib.ptr(rstd4),
-                                                         _lib.fptr(_c(g4)), pw(woe, 1).data_ptr(), _lib.ptr(ev), _lib.ptr(qv),
-                                                         _lib.ptr(kv), _lib.ptr(vv), _lib.ptr(do), _lib.ptr(dz4), _lib.ptr(ds), _lib.ptr(de),
-                                                         _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(dg4), _lib.ptr(db4),
-                                                         ws.data_ptr(), ws.numel(), B, N, C, alpha, _lib.stream_of(dy2f)),
-                               "dg_attn_half_f32_bwd1")
-                _account("attn_half_bwd", 4 * (dy2f.shape[0] * C * (5 if ds is None else 6) + 7 * B * N * C), 2 * dy2f.shape[0] * C * C)
-                de = de.view(B, N, N, C)
-                fused1 = (dq, dk, dv, de)
+                # one launch; ds stays on chip unless a graph is being recorded (the penalty's first backward: its second
+                # order reads ds)
+                dz4, ds, *fused1, dg4, db4 = _half_f32_bwd1(dy2f, pre4, mean4, rstd4, g4, woe, ev, qv, kv, vv, do, alpha,
+                                                            want_aff, not no_graph, inb)
             elif add4 is None and dy2f.shape[0] >= _lib.edge_rows() and ln_bwd_row_gemm_supported(dy2f, C, C):
                 # ln4's backward runs in the producer waves of the out_e input-gradient GEMM (edge-level launches only:
                 # at node level the three small launches it replaces are faster)
@@ -428,35 +543,17 @@ class _AttnBlockBwd(Function):
             dzp, dgp, dbp = row_gemm_ln_bwd(def_, pw(we, 1), C, dz4, ppre, pgamma, pmean, prstd)
         elif want_y:
             dy = row_gemm(def_, pw(we, 1), C, C, residual=dz4).view(y.shape)      # + ln4 residual path
-        use3 = lin3_supported(dqf, (wq, wk, wv))      # dq Wq + dk Wk + dv Wv and the three weight gradients: one launch each
-        if want_x and use3:
-            dx1 = sum3(dqf, dkf, dvf, (wq, wk, wv), residual=dz3).view(x1.shape)   # + ln3 residual path
-        elif want_x:
-            t = row_gemm(dqf, pw(wq, 1), C, C, residual=dz3)                       # + ln3 residual path
-            t = row_gemm(dkf, pw(wk, 1), C, C, residual=t)
-            dx1 = row_gemm(dvf, pw(wv, 1), C, C, residual=t).view(x1.shape)
-        gw = [None] * 12
+        if want_x:
+            dx1 = _qkv_bwd_input((dqf, dkf, dvf), (wq, wk, wv), dz3).view(x1.shape)      # + ln3 residual path
+        gw = {}
         if wants_w:
-            qkv_items = [((dqf, dkf, dvf), x1f, True)] if use3 else [(dqf, x1f, True), (dkf, x1f, True), (dvf, x1f, True)]
-            items = qkv_items + [(def_, yf, True), (dz3, o, True)]
-            if need_edge:
-                items.append((dz4, s, True))
-            # (out_n's weight gradient over the node rows rides in out_e's over the edge rows)
-            res = _wgrad_many(items, open_batch=not inb, pair_from=len(items) - 2 if need_edge else None)
-            if use3:      # rows 0..127 / 128..255 / 256..383 of the stacked gradient
-                (w3, b3), res = res[0], res[1:]
-                gw[0:6] = [w3[0:128], b3[0:128], w3[128:256], b3[128:256], w3[256:384], b3[256:384]]
-            else:
-                (gw[0], gw[1]), (gw[2], gw[3]), (gw[4], gw[5]) = res[:3]
-                res = res[3:]
-            (gw[6], gw[7]), (gw[10], gw[11]) = res[:2]
-            if need_edge:
-                gw[8], gw[9] = res[2]
+            gw = _attn_wgrads((wq, wk, wv), (dqf, dkf, dvf), x1f, (def_, yf), (dz3, o), (dz4, s) if need_edge else None,
+                              want_bias=True, open_batch=not inb)
         ctx.save_for_backward(x1, y, wq, wk, wv, we, woe, won, g3, g4, q, k, v, e, s, o, mean3, rstd3, pre3,
                               mean4, rstd4, pre4, dx2f, dy2f, dz3, dz4, do, ds, dq, dk, dv, de)
         ctx.cfg = (alpha, need_edge, (B, N, C), dx2.shape, None if dy2 is None else dy2.shape)
         ctx.set_materialize_grads(False)
-        return (dx1, dy, *gw, dg3, db3, dg4, db4, dzp, dgp, dbp)
+        return _by_name(_ATTN_BWD_OUT, dict(gw, x1=dx1, y=dy, g3=dg3, b3=db3, g4=dg4, b4=db4, ppre=dzp, pgamma=dgp, pbeta=dbp))
 
     @staticmethod
     @once_differentiable
@@ -471,21 +568,11 @@ class _AttnBlockBwd(Function):
         adt = q.dtype
         pw = lambda w_, m_: packed_weight(w_, m_, adt)
         cast = lambda t: t if t.dtype == adt else t.to(adt)
-        with_w = not _inputs_only()
-        x1f, yf = _c(x1).reshape(-1, C), _c(y).reshape(-1, C)
-        RN, RE = B * N, B * N * N
-        zn = lambda: torch.zeros(RN, C, dtype=adt, device=q.device)
-        t1f = _c(cast(t1)).reshape(-1, C) if t1 is not None else zn()
-        tyf = _c(cast(ty)).reshape(-1, C) if ty is not None else torch.zeros(RE, C, dtype=adt, device=q.device)
+        t1f = _c(cast(t1)).reshape(-1, C) if t1 is not None else torch.zeros(B * N, C, dtype=adt, device=q.device)
+        tyf = _c(cast(ty)).reshape(-1, C) if ty is not None else torch.zeros(B * N * N, C, dtype=adt, device=q.device)
         dqf, dkf, dvf, def_ = dq.view(-1, C), dk.view(-1, C), dv.view(-1, C), de.view(-1, C)
         # adjoints of dq, dk, dv, de (dx1 = dz3 + dq Wq + dk Wk + dv Wv ; dy = dz4 + de We)
-        use3 = lin3_supported(t1f, (wq, wk, wv))
-        if use3:
-            tq, tk, tv = lin3(t1f, (wq, wk, wv), (None, None, None))
-        else:
-            tq = row_gemm(t1f, pw(wq, 0), C, C)
-            tk = row_gemm(t1f, pw(wk, 0), C, C)
-            tv = row_gemm(t1f, pw(wv, 0), C, C)
+        tq, tk, tv = _qkv_fwd(t1f, (wq, wk, wv), (None, None, None))
         te = row_gemm(tyf, pw(we, 0), C, C)
         qv, kv, vv, ev = q.view(B, N, C), k.view(B, N, C), v.view(B, N, C), e.view(B, N, N, C)
         gq, gk, gv, ge, gws, gwo = _attn_bwd2_launch(qv, kv, vv, ev, ds, do, tq.view(B, N, C), tk.view(B, N, C),
@@ -497,46 +584,15 @@ class _AttnBlockBwd(Function):
         if need_edge:
             adz4 = row_gemm(gws.view(-1, C), pw(woe, 0), C, C, residual=tyf)
             z4bar, dy2bar, g4bar = _ln_bwd2_rows(pre4, g4, mean4, rstd4, dy2f, adz4)
-        gW = [None] * 12
-        if with_w:
-            qkv_items = [((dqf, dkf, dvf), t1f, False)] if use3 else [(dqf, t1f, False), (dkf, t1f, False), (dvf, t1f, False)]
-            items = qkv_items + [(def_, tyf, False), (dz3, gwo.view(-1, C), False)]
-            if need_edge:
-                items.append((dz4, gws.view(-1, C), False))
-            res = _wgrad_many(items, pair_from=len(items) - 2 if need_edge else None)
-            if use3:
-                w3, res = res[0][0], res[1:]
-                gW[0], gW[2], gW[4] = w3[0:128], w3[128:256], w3[256:384]
-            else:
-                gW[0], gW[2], gW[4] = (r[0] for r in res[:3])
-                res = res[3:]
-            gW[6], gW[10] = res[0][0], res[1][0]
-            if need_edge:
-                gW[8] = res[2][0]
+        gW = {}
+        if not _inputs_only():
+            gW = _attn_wgrads((wq, wk, wv), (dqf, dkf, dvf), t1f, (def_, tyf), (dz3, gwo.view(-1, C)),
+                              (dz4, gws.view(-1, C)) if need_edge else None, want_bias=False)
         # The outputs depend on x1 / y only through the forward intermediates: their adjoints
         # (z3bar, z4bar at the pre-LayerNorm sums; gq, gk, gv, ge) go to the forward node.
-        # inputs: x1, y, wq,bq, wk,bk, wv,bv, we,be, woe,boe, won,bon, g3, g4, q,k,v,e, s,o,
-        #         mean3,rstd3,pre3, mean4,rstd4,pre4, dx2, dy2, 6 adds, 5 flags, 4 LNHandle fields, want_aff
-        return (None, None, *gW, g3bar, g4bar, gq.view_as(q), gk.view_as(k), gv.view_as(v), ge.view_as(e), None, None,
-                None, None, z3bar, None, None, z4bar, dx2bar.view(dx2_shape),
-                None if dy2bar is None else dy2bar.view(dy2_shape), *([None] * 17))
-
-
-_half_pack_cache = PackCache(1024)
-
-
-def _attn_half_packed(we, woe, dtype):
-    """Fragment-order copies of (e.weight, out_e.weight) and their transposes for the fused attention-half kernels
-    (dg_attn_half_pack), cached like ``packed_weight``."""
-    def make(we, woe):
-        lib = _lib.load()
-        code = _lib.DTYPES[dtype]
-        packed = torch.empty(int(lib.dg_attn_half_packed_bytes(code)), dtype=torch.uint8, device=we.device)
-        with _dev(we):
-            _lib.check(lib.dg_attn_half_pack(_lib.fptr(_c(we.detach())), _lib.fptr(_c(woe.detach())), packed.data_ptr(), code,
-                                             _lib.stream_of(we)), "dg_attn_half_pack")
-        return packed
-    return _half_pack_cache.get((we, woe), (dtype,), make)
+        return _by_name(_ATTN_BWD_IN, dict(gW, g3=g3bar, g4=g4bar, q=gq.view_as(q), k=gk.view_as(k), v=gv.view_as(v),
+                                           e=ge.view_as(e), pre3=z3bar, pre4=z4bar, dx2=dx2bar.view(dx2_shape),
+                                           dy2=None if dy2bar is None else dy2bar.view(dy2_shape)))
 
 
 def _fused_attn_half_enabled() -> bool:
@@ -552,6 +608,9 @@ def attn_half_supported(dtype, N: int, C: int) -> bool:
     return dtype == torch.bfloat16 and C == 128 and 1 <= N <= limit
 
 
+_ATTN_FUSED_IN = _ATTN_TENSORS + ("alpha", "eps3", "eps4", "need_edge")      # _AttnBlockFused.forward
+
+
 class _AttnBlockFused(Function):
     """The same block as ``_AttnBlock`` with the whole EDGE side -- e-projection, Hadamard score, softmax over j, AV,
     out_e, residual, ln4 (reference layers.py:116-135,186-190) -- in ONE kernel per direction (csrc/attn_half.hip):
@@ -565,111 +624,47 @@ class _AttnBlockFused(Function):
         B, N, C = x1.shape
         x1f = _c(x1).reshape(-1, C)
         yc = _c(y)
-        adt = x1f.dtype
-        code = _lib.dt(x1f)
-        pw = lambda w_, m_: packed_weight(w_, m_, adt)
-        q = row_gemm(x1f, pw(wq, 0), C, C, bias=bq)
-        k = row_gemm(x1f, pw(wk, 0), C, C, bias=bk)
-        v = row_gemm(x1f, pw(wv, 0), C, C, bias=bv)
-        lib = _lib.load()
-        dev = x1f.device
-        o = torch.empty_like(q)
-        y2 = pre4 = mean4 = rstd4 = None
-        if need_edge:
-            y2 = torch.empty_like(yc)
-            pre4 = torch.empty_like(yc)
-            mean4 = torch.empty(B * N * N, dtype=torch.float32, device=dev)
-            rstd4 = torch.empty(B * N * N, dtype=torch.float32, device=dev)
-        packed = _attn_half_packed(we, woe, adt)
-        with _dev(q):
-            _lib.check(lib.dg_attn_half_fwd(_lib.ptr(yc), _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), packed.data_ptr(),
-                                            _lib.fptr(_c(be)), _lib.fptr(_c(boe)), _lib.fptr(_c(g4)), _lib.fptr(_c(b4)),
-                                            _lib.ptr(o), _lib.ptr(y2), _lib.ptr(pre4), _lib.ptr(mean4), _lib.ptr(rstd4),
-                                            B, N, C, alpha, eps4, code, _lib.stream_of(q)), "dg_attn_half_fwd")
-        es = q.element_size()
-        _account("attn_half_fwd", es * B * ((3 if need_edge else 1) * N * N * C + 4 * N * C),
-                 2 * B * N * N * C * C * (2 if need_edge else 1), floor=es * B * ((2 if need_edge else 1) * N * N * C + 4 * N * C))
-        x2, mean3, rstd3, pre3 = row_gemm(o, pw(won, 0), C, C, bias=bon, residual=x1f, ln=(_c(g3), _c(b3), eps3),
-                                          want_pre=True)
-        ctx.save_for_backward(x1, yc, wq, wk, wv, we, woe, won, g3, g4, be, q, k, v, o, mean3, rstd3, pre3, mean4, rstd4,
-                              pre4)
+        q, k, v = _qkv_fwd(x1f, (wq, wk, wv), (bq, bk, bv))
+        o, y2, pre4, mean4, rstd4 = _half_fwd(yc, q, k, v, we, be, woe, boe, g4, b4, B, N, C, alpha, eps4, need_edge)
+        x2, mean3, rstd3, pre3 = row_gemm(o, packed_weight(won, 0, x1f.dtype), C, C, bias=bon, residual=x1f,
+                                          ln=(_c(g3), _c(b3), eps3), want_pre=True)
+        ctx.save_for_backward(x1, yc, wq, wk, wv, we, woe, won, g3, g4, be, q, k, v, o, mean3, rstd3, pre3, mean4, rstd4, pre4)
         ctx.cfg = (alpha, need_edge, (B, N, C))
         ctx.extra = (bq, bk, bv, boe, bon, b3, b4, eps3, eps4)
         ctx.set_materialize_grads(False)
-        if need_edge:
-            return x2.view(B, N, C), y2
-        return x2.view(B, N, C)
+        return (x2.view(B, N, C), y2) if need_edge else x2.view(B, N, C)
 
     @staticmethod
     def backward(ctx, dx2, dy2=None):
-        wants_w = bool((ctx.needs_input_grad[2] or any(ctx.needs_input_grad[14:18])) and not _inputs_only()
-                       and not torch.is_grad_enabled())
-        with _reduce_batch(ctx.saved_tensors[0], on=wants_w) as inb:      # one reduce launch for the block
-            return _AttnBlockFused._backward(ctx, inb, dx2, dy2)
-
-    @staticmethod
-    def _backward(ctx, inb, dx2, dy2=None):
+        needs = dict(zip(_ATTN_FUSED_IN, ctx.needs_input_grad))
         alpha, need_edge, (B, N, C) = ctx.cfg
-        (x1, y, wq, wk, wv, we, woe, won, g3, g4, be, q, k, v, o, mean3, rstd3, pre3, mean4, rstd4,
-         pre4) = ctx.saved_tensors
+        x1, y, wq, wk, wv, we, woe, won, g3, g4, be, q, k, v, o, mean3, rstd3, pre3, mean4, rstd4, pre4 = ctx.saved_tensors
         if torch.is_grad_enabled():      # create_graph=True outside second_order_forward(): composite graph
             bq, bk, bv, boe, bon, b3, b4, eps3, eps4 = ctx.extra
             ins = (x1, y, wq, bq, wk, bk, wv, bv, we, be, woe, boe, won, bon, g3, b3, g4, b4)
             gouts = (dx2, dy2) if need_edge else dx2
-            return _double_backward_fallback(
-                lambda *t: _composite_attn_block(*t, alpha, eps3, eps4, need_edge), ins, gouts) + (None,) * 4
-        adt = q.dtype
-        code = _lib.dt(q)
-        dev = q.device
-        pw = lambda w_, m_: packed_weight(w_, m_, adt)
-        cast = lambda t: t if t.dtype == adt else t.to(adt)
-        wants_w = ctx.needs_input_grad[2] and not _inputs_only()
-        want_aff = any(ctx.needs_input_grad[14:18]) and not _inputs_only()
-        x1f = _c(x1).reshape(-1, C)
-        if dx2 is None:
-            dx2 = torch.zeros_like(pre3)
-        dz3, dg3, db3 = _ln_bwd_rows(pre3, g3, mean3, rstd3, _c(cast(dx2)).reshape(-1, C), want_affine=want_aff,
-                                     batch_slot=0 if inb else None)
-        do = row_gemm(dz3, pw(won, 1), C, C)
-        dz4 = dg4 = db4 = None
-        if need_edge:
-            if dy2 is None:
-                dy2 = torch.zeros_like(pre4)
-            dz4, dg4, db4 = _ln_bwd_rows(pre4.view(-1, C), g4, mean4, rstd4, _c(cast(dy2)).reshape(-1, C), want_affine=want_aff,
-                                         batch_slot=1 if inb else None)
-        lib = _lib.load()
-        dy = torch.empty_like(y)
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
-        dwe = dbe = dwoe = dboe = None
-        if wants_w:
-            dwe = torch.empty_like(we)
-            dbe = torch.empty(C, dtype=torch.float32, device=dev)
+            return _by_name(_ATTN_FUSED_IN, dict(zip(_ATTN_TENSORS, _double_backward_fallback(
+                lambda *t: _composite_attn_block(*t, alpha, eps3, eps4, need_edge), ins, gouts))))
+        rows = lambda t: _c(t if t.dtype == q.dtype else t.to(q.dtype)).reshape(-1, C)
+        wants_w = needs["wq"] and not _inputs_only()
+        want_aff = any(needs[n] for n in _ATTN_AFFINE) and not _inputs_only()
+        with _reduce_batch(x1, on=bool(wants_w or want_aff)) as inb:      # one reduce launch for the block
+            dz3, dg3, db3, do = _ln3_bwd_do(pre3, g3, mean3, rstd3, rows(torch.zeros_like(pre3) if dx2 is None else dx2), None,
+                                            won, want_aff, inb)
+            dz4 = dg4 = db4 = None
             if need_edge:
-                dwoe = torch.empty_like(woe)
-                dboe = torch.empty(C, dtype=torch.float32, device=dev)
-        need = int(lib.dg_attn_half_bwd_workspace_bytes(B, N))
-        with _dev(q):
-            ws = _scratch(q, need, "half")
-            _lib.check(lib.dg_attn_half_bwd(_lib.ptr(y), _lib.ptr(dz4), _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(do),
-                                            _attn_half_packed(we, woe, adt).data_ptr(), _lib.fptr(_c(be)), _lib.ptr(dy),
-                                            _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(dwe), _lib.ptr(dbe),
-                                            _lib.ptr(dwoe), _lib.ptr(dboe), ws.data_ptr(), ws.numel(), B, N, C, alpha,
-                                            code, _lib.stream_of(q)), "dg_attn_half_bwd")
-        es = q.element_size()
-        _account("attn_half_bwd", es * B * ((3 if need_edge else 2) * N * N * C + 8 * N * C),
-                 2 * B * N * N * C * C * ((3 if need_edge else 2) + (2 if wants_w and need_edge else (1 if wants_w else 0))))
-        dx1 = None
-        if ctx.needs_input_grad[0]:
-            t = row_gemm(dq, pw(wq, 1), C, C, residual=dz3)                        # + ln3 residual path
-            t = row_gemm(dk, pw(wk, 1), C, C, residual=t)
-            dx1 = row_gemm(dv, pw(wv, 1), C, C, residual=t).view(x1.shape)
-        gw = [None] * 12
-        if wants_w:
-            (gw[0], gw[1]), (gw[2], gw[3]), (gw[4], gw[5]), (gw[10], gw[11]) = _wgrad_many(
-                [(dq, x1f, True), (dk, x1f, True), (dv, x1f, True), (dz3, o, True)], open_batch=not inb)
-            gw[6], gw[7] = dwe, dbe
-            gw[8], gw[9] = dwoe, dboe
-        return (dx1, (dy if ctx.needs_input_grad[1] else None), *gw, dg3, db3, dg4, db4, None, None, None, None)
+                dz4, dg4, db4 = _ln_bwd_rows(pre4.view(-1, C), g4, mean4, rstd4, rows(torch.zeros_like(pre4) if dy2 is None else dy2),
+                                             want_affine=want_aff, batch_slot=1 if inb else None)
+            dy, dq, dk, dv, dwe, dbe, dwoe, dboe = _half_bwd(y, dz4, q, k, v, do, we, be, woe, B, N, C, alpha, wants_w, need_edge)
+            dx1 = None
+            if needs["x1"]:
+                dx1 = _qkv_bwd_input((dq, dk, dv), (wq, wk, wv), dz3).view(x1.shape)      # + ln3 residual path
+            gw = {}
+            if wants_w:      # (e / out_e: their gradients come out of the kernel)
+                gw = _attn_wgrads((wq, wk, wv), (dq, dk, dv), _c(x1).reshape(-1, C), None, (dz3, o), None, want_bias=True,
+                                  open_batch=not inb)
+                gw.update(we=dwe, be=dbe, woe=dwoe, boe=dboe)
+        return _by_name(_ATTN_FUSED_IN, dict(gw, x1=dx1, y=dy if needs["y"] else None, g3=dg3, b3=db3, g4=dg4, b4=db4))
 
 
 def attn_block(x1, y, attn, ln3, ln4, need_edge=True, y_ln=None):
@@ -685,15 +680,18 @@ def attn_block(x1, y, attn, ln3, ln4, need_edge=True, y_ln=None):
              and all(t is not None for t in args))
     if not fused:
         out = _composite_attn_block(*args, alpha, ln3.eps, ln4.eps, need_edge)
-    elif (not in_second_order_forward() and attn_half_supported(x1.dtype, x1.shape[1], C) and _fused_attn_half_enabled()
-          and tuple(y.shape) == (x1.shape[0], x1.shape[1], x1.shape[1], C)):
+        return out if need_edge else (out, None)
+    if (not in_second_order_forward() and attn_half_supported(x1.dtype, x1.shape[1], C) and _fused_attn_half_enabled()
+            and tuple(y.shape) == (x1.shape[0], x1.shape[1], x1.shape[1], C)):
         out = _AttnBlockFused.apply(*args, alpha, ln3.eps, ln4.eps, need_edge)
-        return (out[0], out[1]) if need_edge else (out, None)
-    else:
-        prev = (None,) * 5 if y_ln is None else (y_ln.pre, y_ln.mean, y_ln.rstd, y_ln.gamma, y_ln.beta)
-        out = _AttnBlock.apply(*args, alpha, ln3.eps, ln4.eps, need_edge, *prev)
-        return (out[0], out[1]) if need_edge else (out[0], None)
-    return out if need_edge else (out, None)
+        return tuple(out) if need_edge else (out, None)
+    prev = (None,) * len(_LN_HANDLE) if y_ln is None else (y_ln.pre, y_ln.mean, y_ln.rstd, y_ln.gamma, y_ln.beta)
+    out = _AttnBlock.apply(*args, alpha, ln3.eps, ln4.eps, need_edge, *prev)
+    if need_edge:
+        x2, y2, *_ = out      # _ATTN_OUT_EDGE
+        return x2, y2
+    x2, *_ = out              # _ATTN_OUT_NODE
+    return x2, None
 
 
 __all__ = [_n for _n in dir() if not _n.startswith("__")]
