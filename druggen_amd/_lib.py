@@ -8,6 +8,7 @@ call fails loudly.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import threading
@@ -188,6 +189,13 @@ def check(status: int, what: str) -> None:
         raise RuntimeError(f"{what} failed ({status}): {msg.decode() if msg else '?'}")
 
 
+def _dev(t):
+    """Run the launch with t's device current (nn.DataParallel replica threads)."""
+    if torch.cuda.current_device() == t.device.index:
+        return contextlib.nullcontext()
+    return torch.cuda.device(t.device)
+
+
 DTYPES = {torch.float32: 0, torch.bfloat16: 1}     # DG_DTYPE_F32 / DG_DTYPE_BF16 of include/druggen_hip.h
 F32_H16 = 2      # DG_DTYPE_F32_H16: float32 activations, the [R,384] feed-forward hidden tensors as one scaled fp16 plane
 F32_H24 = 3      # DG_DTYPE_F32_H24: ... as the top 24 bits of every float32 (three bytes per element)
@@ -235,6 +243,17 @@ def stream_of(t) -> int:
     if _raw_stream is not None:
         return _raw_stream(t.device.index)
     return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def launch(name: str, ref, *args) -> None:
+    """Call the entry ``name`` -- one whose last parameter is ``dg_stream_t stream`` -- with ``ref``'s device current, on the
+    caller's stream there: ``name(*args, stream_of(ref))``, a non-zero status raised as by ``check``.  The ptr / fptr
+    conversions stay in the caller's argument list: they are evaluated, and raise, before anything here runs."""
+    entry = getattr(load(), name)
+    with _dev(ref):
+        status = entry(*args, stream_of(ref))
+    if status != 0:
+        check(status, name)
 
 
 # ---- profiler ---------------------------------------------------------------

@@ -12,7 +12,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .functional import _dev, attach_one_hot_labels
+from .functional import attach_one_hot_labels
 
 __all__ = ["dense_one_hot_adjacency", "load_molecules", "label2onehot", "raise_deferred_checks"]
 
@@ -84,7 +84,6 @@ def dense_one_hot_adjacency(edge_index, edge_attr, batch_size: int, vertexes: in
     ``dst mod N`` -- what ``to_dense_adj`` does with ``dst - ptr[batch[dst]]``."""
     if not edge_index.is_cuda:
         raise RuntimeError("druggen_amd.data runs on the GPU (no CPU fallback)")
-    lib = _lib.load()
     dev = edge_index.device
     src = edge_index[0].contiguous().long()
     dst = edge_index[1].contiguous().long()
@@ -92,10 +91,8 @@ def dense_one_hot_adjacency(edge_index, edge_attr, batch_size: int, vertexes: in
     labels = torch.empty(batch_size, vertexes, vertexes, dtype=torch.int32, device=dev)
     a = torch.empty(batch_size, vertexes, vertexes, b_dim, dtype=torch.float32, device=dev)
     bad = torch.empty(1, dtype=torch.int32, device=dev)
-    with _dev(a):
-        _lib.check(lib.dg_densify(src.data_ptr(), dst.data_ptr(), attr.data_ptr(), src.numel(), batch_size, vertexes,
-                                  b_dim, labels.data_ptr(), a.data_ptr(), bad.data_ptr(), _lib.stream_of(a)),
-                   "dg_densify")
+    _lib.launch("dg_densify", a, src.data_ptr(), dst.data_ptr(), attr.data_ptr(), src.numel(), batch_size, vertexes, b_dim,
+                labels.data_ptr(), a.data_ptr(), bad.data_ptr())
     if check == "deferred":
         raise_deferred_checks()      # counters of earlier batches whose host copies are complete by now
         # counter -> pinned host memory on a SIDE stream that waits for the densify kernel: the compute stream sees one event

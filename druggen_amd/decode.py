@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .functional import _c, _dev
+from .functional import _c
 
 __all__ = ["argmax_labels", "decode_molecule_labels", "decode_molecule_graphs", "MoleculeBatch"]
 
@@ -24,9 +24,7 @@ def argmax_labels(logits):
     E = x.shape[-1]
     rows = x.numel() // E
     out = torch.empty(x.shape[:-1], dtype=torch.uint8, device=x.device)
-    with _dev(x):
-        _lib.check(_lib.load().dg_argmax_decode(_lib.ptr(x), rows, E, out.data_ptr(), _lib.stream_of(x)),
-                   "dg_argmax_decode")
+    _lib.launch("dg_argmax_decode", x, _lib.ptr(x), rows, E, out.data_ptr())
     return out
 
 
@@ -176,10 +174,8 @@ def decode_molecule_graphs(node_sample, edge_sample, *, bond_order2=None, bond_c
         raise ValueError("out= must be a device MoleculeBatch of this batch's B, N, bond_cap and valence2 choice")
     if B == 0:
         return out
-    with _dev(x):
-        _lib.check(_lib.load().dg_decode_graph(
-            _lib.fptr(x), _lib.fptr(e), None if order2 is None else order2.data_ptr(), B, N, M, E, cap,
-            out.atoms.data_ptr(), out.bonds.data_ptr() if cap > 0 else None, out.n_bonds.data_ptr(),
-            out.component.data_ptr(), out.n_components.data_ptr(), out.largest.data_ptr(), out.largest_size.data_ptr(),
-            None if order2 is None else out.valence2.data_ptr(), _lib.stream_of(x)), "dg_decode_graph")
+    _lib.launch("dg_decode_graph", x, _lib.fptr(x), _lib.fptr(e), None if order2 is None else order2.data_ptr(), B, N, M, E,
+                cap, out.atoms.data_ptr(), out.bonds.data_ptr() if cap > 0 else None, out.n_bonds.data_ptr(),
+                out.component.data_ptr(), out.n_components.data_ptr(), out.largest.data_ptr(), out.largest_size.data_ptr(),
+                None if order2 is None else out.valence2.data_ptr())
     return out

@@ -6,8 +6,9 @@ second-order kernel.  That keeps the reference's gradient penalty
 (``src/model/loss.py:32-39``: ``autograd.grad(..., create_graph=True)`` followed
 by ``d_loss.backward()``, ``train.py:367``) working unchanged on these modules.
 
-One module per autograd node family, layered (each imports the ones before it; this package re-exports all of them, private
-helpers included, so ``druggen_amd.functional.<name>`` resolves whatever module ``<name>`` lives in):
+One module per autograd node family, layered: a module imports, by name, what it uses from the ones before it.  This package
+gathers what every module defines, private helpers included, into one flat namespace, so ``druggen_amd.functional.<name>``
+resolves whatever module ``<name>`` lives in:
 
     _runtime    shared state: traffic accounting, hidden-tensor storage modes, workspaces, activation dtype, pass flags,
                 reduce-batch / riding-launch scopes, the packed-weight cache (``PackCache``: one freshness rule, alias
@@ -21,14 +22,14 @@ helpers included, so ``druggen_amd.functional.<name>`` resolves whatever module 
 """
 from __future__ import annotations
 
-from . import _runtime, layernorm, dense, heads, ffn, attention, embed      # noqa: F401
-from ._runtime import *      # noqa: F401,F403
-from .layernorm import *     # noqa: F401,F403
-from .dense import *       # noqa: F401,F403
-from .heads import *         # noqa: F401,F403
-from .ffn import *           # noqa: F401,F403
-from .attention import *     # noqa: F401,F403
-from .embed import *         # noqa: F401,F403
+import types
+
+from . import _runtime, layernorm, dense, heads, ffn, attention, embed
+
+# the flat namespace: a name that appears in two modules was imported by one from the other, so it is one object
+for _m in (_runtime, layernorm, dense, heads, ffn, attention, embed):
+    globals().update((_k, _v) for _k, _v in vars(_m).items() if not _k.startswith("__") and not isinstance(_v, types.ModuleType))
+del _m, types
 
 __all__ = ["attach_one_hot_labels", "attn_core", "ln_residual", "linear", "linear_relu", "linear_ln", "ffn_ln", "attn_block", "embed_sym", "inputs_only_backward",
            "second_order_forward", "in_second_order_forward", "readout", "traffic_reset", "traffic_bytes", "traffic_flops", "traffic_floor_bytes",

@@ -4,13 +4,10 @@ thread-local scopes of the C library (reduce batches, riding launches)."""
 from __future__ import annotations
 
 import contextlib
-import ctypes
 import threading
 import weakref
 
 import torch
-from torch.autograd import Function
-from torch.autograd.function import once_differentiable
 
 from .. import _lib
 from ..options import options
@@ -66,11 +63,7 @@ def traffic_flops(kernel: str) -> int:
     return _traffic.get(kernel + ":flops", 0)
 
 
-def _dev(t):
-    """Run the launch with t's device current (nn.DataParallel replica threads)."""
-    if torch.cuda.current_device() == t.device.index:
-        return contextlib.nullcontext()
-    return torch.cuda.device(t.device)
+_dev = _lib._dev      # (lives next to ``_lib.launch``, which needs it)
 
 
 def _c(t):
@@ -313,13 +306,12 @@ def _reduce_batch(ref, on=True):
     if not (on and ref.is_cuda):
         yield False
         return
-    lib = _lib.load()
     with _dev(ref):
-        _lib.check(lib.dg_linear_wgrad_batch_begin(), "dg_linear_wgrad_batch_begin")
+        _lib.check(_lib.load().dg_linear_wgrad_batch_begin(), "dg_linear_wgrad_batch_begin")
         try:
             yield True
         finally:
-            _lib.check(lib.dg_linear_wgrad_batch_end(_lib.stream_of(ref)), "dg_linear_wgrad_batch_end")
+            _lib.launch("dg_linear_wgrad_batch_end", ref)
 
 
 _pair_tls = threading.local()
@@ -343,17 +335,16 @@ def _pair_launches(ref, on=True):
     if not (on and ref.is_cuda):
         yield False
         return
-    lib = _lib.load()
     outer = getattr(_pair_tls, "keep", None)
     if outer is None:
         _pair_tls.keep = []
     with _dev(ref):
-        _lib.check(lib.dg_launch_pair_begin(), "dg_launch_pair_begin")
+        _lib.check(_lib.load().dg_launch_pair_begin(), "dg_launch_pair_begin")
         try:
             yield True
         finally:
             try:      # (also on an exception path: whatever waits is launched before its operands can be freed)
-                _lib.check(lib.dg_launch_pair_end(_lib.stream_of(ref)), "dg_launch_pair_end")
+                _lib.launch("dg_launch_pair_end", ref)
             finally:
                 if outer is None:
                     _pair_tls.keep = None
@@ -499,6 +490,3 @@ def bump_weights_epoch() -> None:
     if sum(len(c) for c in caches) > _EPOCH_SWEEP_ABOVE:
         for c in caches:
             c.sweep()
-
-
-__all__ = [_n for _n in dir() if not _n.startswith("__")]

@@ -8,11 +8,11 @@ from torch.autograd.function import once_differentiable
 
 from .. import _lib
 from ..options import options
-from ._runtime import *      # noqa: F401,F403
-from .layernorm import *      # noqa: F401,F403
-from .dense import *      # noqa: F401,F403
-from .heads import *      # noqa: F401,F403
-from .ffn import *      # noqa: F401,F403
+from ._runtime import (_account, _alias_outputs_enabled, _c, in_second_order_forward, _inputs_only, PackCache, _reduce_batch,
+                       _scratch, _weight_alias)
+from .dense import (_double_backward_fallback, _join_alias_grads, lin3, lin3_supported, linear, linear_ln, _ln_bwd2_rows,
+                    ln_bwd_row_gemm, ln_bwd_row_gemm_supported, _ln_bwd_rows, packed_weight, row_gemm, row_gemm_ln_bwd,
+                    row_gemm_ln_bwd_supported, sum3, _wgrad_many)
 
 
 # --------------------------------------------------------------------------
@@ -44,12 +44,8 @@ def _long_workspace(q, B, N, C):
 def _core_fwd(q, k, v, e, s, o, alpha, B, N, C):
     """One attention-core forward launch: dg_attn_core_fwd up to 96 neighbours, dg_attn_core_long_fwd above."""
     _check_neighbours(N)
-    lib = _lib.load()
-    fn, name = (lib.dg_attn_core_fwd, "dg_attn_core_fwd") if N <= ATTN_SHORT_MAX_N else (lib.dg_attn_core_long_fwd,
-                                                                                          "dg_attn_core_long_fwd")
-    with _dev(q):
-        _lib.check(fn(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(e), _lib.ptr(s), _lib.ptr(o), B, N, C, alpha,
-                      _lib.dt(q), _lib.stream_of(q)), name)
+    _lib.launch("dg_attn_core_fwd" if N <= ATTN_SHORT_MAX_N else "dg_attn_core_long_fwd", q, _lib.ptr(q), _lib.ptr(k), _lib.ptr(v),
+                _lib.ptr(e), _lib.ptr(s), _lib.ptr(o), B, N, C, alpha, _lib.dt(q))
     _account("attn_fwd", q.element_size() * B * ((2 if s is not None else 1) * N * N * C + 4 * N * C))
 
 
@@ -57,21 +53,16 @@ def _core_bwd(q, k, v, e, ws, wo, add_e, dq, dk, dv, de, alpha):
     """One first-order attention-core backward launch (dg_attn_core_bwd_add / dg_attn_core_long_bwd)."""
     B, N, C = q.shape[0], q.shape[1], q.shape[2]
     _check_neighbours(N)
-    lib = _lib.load()
     extra = 0
-    with _dev(q):
-        if N <= ATTN_SHORT_MAX_N:
-            _lib.check(lib.dg_attn_core_bwd_add(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(e), _lib.ptr(ws),
-                                                _lib.ptr(wo), _lib.ptr(add_e), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv),
-                                                _lib.ptr(de), B, N, C, alpha, _lib.dt(q), _lib.stream_of(q)),
-                       "dg_attn_core_bwd")
-        else:
-            work, extra = _long_workspace(q, B, N, C)
-            wp = work.data_ptr() if extra else None
-            _lib.check(lib.dg_attn_core_long_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(e), _lib.ptr(ws),
-                                                 _lib.ptr(wo), _lib.ptr(add_e), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv),
-                                                 _lib.ptr(de), wp, extra, B, N, C, alpha, _lib.dt(q), _lib.stream_of(q)),
-                       "dg_attn_core_long_bwd")
+    if N <= ATTN_SHORT_MAX_N:
+        _lib.launch("dg_attn_core_bwd_add", q, _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(e), _lib.ptr(ws), _lib.ptr(wo),
+                    _lib.ptr(add_e), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(de), B, N, C, alpha, _lib.dt(q))
+    else:
+        work, extra = _long_workspace(q, B, N, C)
+        wp = work.data_ptr() if extra else None
+        _lib.launch("dg_attn_core_long_bwd", q, _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(e), _lib.ptr(ws),
+                    _lib.ptr(wo), _lib.ptr(add_e), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(de), wp, extra, B, N, C,
+                    alpha, _lib.dt(q))
     base = q.element_size() * B * ((2 + (ws is not None) + (add_e is not None)) * N * N * C + 7 * N * C)
     _account("attn_bwd", base + 2 * extra, floor=base)      # (long path: the column partials are written and read once)
 
@@ -80,17 +71,14 @@ def _core_bwd2(q, k, v, e, ws, wo, tq, tk, tv, te, gq, gk, gv, ge, gws, gwo, alp
     """One second-order attention-core launch (dg_attn_core_bwd2 / dg_attn_core_long_bwd2)."""
     B, N, C = q.shape[0], q.shape[1], q.shape[2]
     _check_neighbours(N)
-    lib = _lib.load()
     extra = 0
     args = [_lib.ptr(x) for x in (q, k, v, e, ws, wo, tq, tk, tv, te, gq, gk, gv, ge, gws, gwo)]
-    with _dev(q):
-        if N <= ATTN_SHORT_MAX_N:
-            _lib.check(lib.dg_attn_core_bwd2(*args, B, N, C, alpha, _lib.dt(q), _lib.stream_of(q)), "dg_attn_core_bwd2")
-        else:
-            work, extra = _long_workspace(q, B, N, C)
-            wp = work.data_ptr() if extra else None
-            _lib.check(lib.dg_attn_core_long_bwd2(*args, wp, extra, B, N, C, alpha, _lib.dt(q),
-                                                  _lib.stream_of(q)), "dg_attn_core_long_bwd2")
+    if N <= ATTN_SHORT_MAX_N:
+        _lib.launch("dg_attn_core_bwd2", q, *args, B, N, C, alpha, _lib.dt(q))
+    else:
+        work, extra = _long_workspace(q, B, N, C)
+        wp = work.data_ptr() if extra else None
+        _lib.launch("dg_attn_core_long_bwd2", q, *args, wp, extra, B, N, C, alpha, _lib.dt(q))
     base = q.element_size() * B * ((5 if ws is not None else 3) * N * N * C + 11 * N * C)
     _account("attn_bwd2", base + 2 * extra, floor=base)
 
@@ -265,16 +253,14 @@ def _ln3_bwd_do(pre3, g3, mean3, rstd3, dx2f, add3, won, want_aff, inb):
 def _half_f32_fwd(yf, q, k, v, we, be, woe, boe, g4, b4, B, N, C, alpha, eps4, keep):
     """e projection, scores, softmax / node output, out_e, residual, ln4: one launch (dg_attn_half_f32_fwd); e, s and the
     pre-LayerNorm sum are written for the backward only (``keep``).  Returns (e, s, o, y2, pre4, mean4, rstd4)."""
-    lib, P, F = _lib.load(), _lib.ptr, _lib.fptr
+    P, F = _lib.ptr, _lib.fptr
     R = yf.shape[0]
     e, s, pre4 = (torch.empty_like(yf) if keep else None for _ in range(3))
     o, y2 = torch.empty_like(q), torch.empty_like(yf)
     mean4, rstd4 = (torch.empty(R, dtype=torch.float32, device=yf.device) for _ in range(2))
-    with _dev(q):
-        _lib.check(lib.dg_attn_half_f32_fwd(P(yf), P(q), P(k), P(v), packed_weight(we, 0, yf.dtype).data_ptr(), F(_c(be)),
-                                            packed_weight(woe, 0, yf.dtype).data_ptr(), F(_c(boe)), F(_c(g4)), F(_c(b4)), P(e), P(s),
-                                            P(o), P(y2), P(pre4), P(mean4), P(rstd4), B, N, C, alpha, eps4, _lib.stream_of(q)),
-                   "dg_attn_half_f32_fwd")
+    _lib.launch("dg_attn_half_f32_fwd", q, P(yf), P(q), P(k), P(v), packed_weight(we, 0, yf.dtype).data_ptr(), F(_c(be)),
+                packed_weight(woe, 0, yf.dtype).data_ptr(), F(_c(boe)), F(_c(g4)), F(_c(b4)), P(e), P(s), P(o), P(y2),
+                P(pre4), P(mean4), P(rstd4), B, N, C, alpha, eps4)
     _account("attn_half_fwd", 4 * (R * C * (5 if keep else 2) + 4 * B * N * C), 4 * R * C * C,
              floor=4 * (R * C * 2 + 4 * B * N * C))
     return e, s, o, y2, pre4, mean4, rstd4
@@ -290,12 +276,11 @@ def _half_f32_bwd1(dy2f, pre4, mean4, rstd4, g4, woe, ev, qv, kv, vv, do, alpha,
     ds = torch.empty_like(dy2f).view(B, N, N, C) if keep_ds else None
     dq, dk, dv = (torch.empty(B, N, C, dtype=adt, device=dev) for _ in range(3))
     dg4, db4 = (torch.empty(2, C, dtype=torch.float32, device=dev).unbind(0) if want_aff else (None, None))
-    with _dev(dy2f):
-        ws = _scratch(dy2f, int(lib.dg_attn_half_f32_bwd1_workspace_bytes(B)), "ahb_batch" if inb else "ahb")
-        woe_t = packed_weight(woe, 1, adt).data_ptr()
-        _lib.check(lib.dg_attn_half_f32_bwd1(P(dy2f), P(pre4), P(mean4), P(rstd4), _lib.fptr(_c(g4)), woe_t, P(ev), P(qv), P(kv), P(vv),
-                                             P(do), P(dz4), P(ds), P(de), P(dq), P(dk), P(dv), P(dg4), P(db4), ws.data_ptr(), ws.numel(),
-                                             B, N, C, alpha, _lib.stream_of(dy2f)), "dg_attn_half_f32_bwd1")
+    ws = _scratch(dy2f, int(lib.dg_attn_half_f32_bwd1_workspace_bytes(B)), "ahb_batch" if inb else "ahb")
+    woe_t = packed_weight(woe, 1, adt).data_ptr()
+    _lib.launch("dg_attn_half_f32_bwd1", dy2f, P(dy2f), P(pre4), P(mean4), P(rstd4), _lib.fptr(_c(g4)), woe_t, P(ev), P(qv),
+                P(kv), P(vv), P(do), P(dz4), P(ds), P(de), P(dq), P(dk), P(dv), P(dg4), P(db4), ws.data_ptr(), ws.numel(), B,
+                N, C, alpha)
     _account("attn_half_bwd", 4 * (dy2f.shape[0] * C * (5 if ds is None else 6) + 7 * B * N * C), 2 * dy2f.shape[0] * C * C)
     return dz4, ds, dq, dk, dv, de.view(B, N, N, C), dg4, db4
 
@@ -310,9 +295,7 @@ def _attn_half_packed(we, woe, dtype):
         lib = _lib.load()
         code = _lib.DTYPES[dtype]
         packed = torch.empty(int(lib.dg_attn_half_packed_bytes(code)), dtype=torch.uint8, device=we.device)
-        with _dev(we):
-            _lib.check(lib.dg_attn_half_pack(_lib.fptr(_c(we.detach())), _lib.fptr(_c(woe.detach())), packed.data_ptr(), code,
-                                             _lib.stream_of(we)), "dg_attn_half_pack")
+        _lib.launch("dg_attn_half_pack", we, _lib.fptr(_c(we.detach())), _lib.fptr(_c(woe.detach())), packed.data_ptr(), code)
         return packed
     return _half_pack_cache.get((we, woe), (dtype,), make)
 
@@ -320,15 +303,13 @@ def _attn_half_packed(we, woe, dtype):
 def _half_fwd(yc, q, k, v, we, be, woe, boe, g4, b4, B, N, C, alpha, eps4, need_edge):
     """The whole edge side of the block in one launch (dg_attn_half_fwd): e and s never exist in HBM.  Returns
     (o, y2, pre4, mean4, rstd4); the last four are None without ``need_edge``."""
-    lib, P, F = _lib.load(), _lib.ptr, _lib.fptr
+    P, F = _lib.ptr, _lib.fptr
     o = torch.empty_like(q)
     y2, pre4 = (torch.empty_like(yc) if need_edge else None for _ in range(2))
     mean4, rstd4 = (torch.empty(B * N * N, dtype=torch.float32, device=q.device) if need_edge else None for _ in range(2))
     packed = _attn_half_packed(we, woe, q.dtype)
-    with _dev(q):
-        _lib.check(lib.dg_attn_half_fwd(P(yc), P(q), P(k), P(v), packed.data_ptr(), F(_c(be)), F(_c(boe)), F(_c(g4)), F(_c(b4)), P(o),
-                                        P(y2), P(pre4), P(mean4), P(rstd4), B, N, C, alpha, eps4, _lib.dt(q), _lib.stream_of(q)),
-                   "dg_attn_half_fwd")
+    _lib.launch("dg_attn_half_fwd", q, P(yc), P(q), P(k), P(v), packed.data_ptr(), F(_c(be)), F(_c(boe)), F(_c(g4)),
+                F(_c(b4)), P(o), P(y2), P(pre4), P(mean4), P(rstd4), B, N, C, alpha, eps4, _lib.dt(q))
     es = q.element_size()
     _account("attn_half_fwd", es * B * ((3 if need_edge else 1) * N * N * C + 4 * N * C),
              2 * B * N * N * C * C * (2 if need_edge else 1), floor=es * B * ((2 if need_edge else 1) * N * N * C + 4 * N * C))
@@ -346,11 +327,10 @@ def _half_bwd(y, dz4, q, k, v, do, we, be, woe, B, N, C, alpha, wants_w, need_ed
         dwe, dbe = torch.empty_like(we), torch.empty(C, dtype=torch.float32, device=q.device)
     if wants_w and need_edge:
         dwoe, dboe = torch.empty_like(woe), torch.empty(C, dtype=torch.float32, device=q.device)
-    with _dev(q):
-        ws = _scratch(q, int(lib.dg_attn_half_bwd_workspace_bytes(B, N)), "half")
-        _lib.check(lib.dg_attn_half_bwd(P(y), P(dz4), P(q), P(k), P(v), P(do), _attn_half_packed(we, woe, q.dtype).data_ptr(),
-                                        _lib.fptr(_c(be)), P(dy), P(dq), P(dk), P(dv), P(dwe), P(dbe), P(dwoe), P(dboe), ws.data_ptr(),
-                                        ws.numel(), B, N, C, alpha, _lib.dt(q), _lib.stream_of(q)), "dg_attn_half_bwd")
+    ws = _scratch(q, int(lib.dg_attn_half_bwd_workspace_bytes(B, N)), "half")
+    _lib.launch("dg_attn_half_bwd", q, P(y), P(dz4), P(q), P(k), P(v), P(do), _attn_half_packed(we, woe, q.dtype).data_ptr(),
+                _lib.fptr(_c(be)), P(dy), P(dq), P(dk), P(dv), P(dwe), P(dbe), P(dwoe), P(dboe), ws.data_ptr(), ws.numel(), B,
+                N, C, alpha, _lib.dt(q))
     es = q.element_size()
     _account("attn_half_bwd", es * B * ((3 if need_edge else 2) * N * N * C + 8 * N * C),
              2 * B * N * N * C * C * ((3 if need_edge else 2) + (2 if wants_w and need_edge else (1 if wants_w else 0))))
@@ -692,6 +672,3 @@ def attn_block(x1, y, attn, ln3, ln4, need_edge=True, y_ln=None):
         return x2, y2
     x2, *_ = out              # _ATTN_OUT_NODE
     return x2, None
-
-
-__all__ = [_n for _n in dir() if not _n.startswith("__")]

@@ -3,8 +3,6 @@ epilogue (dg_row_gemm*), three Linears per launch (q / k / v), LayerNorm backwar
 from __future__ import annotations
 
 import contextlib
-import ctypes
-import threading
 
 import torch
 from torch.autograd import Function
@@ -12,8 +10,10 @@ from torch.autograd.function import once_differentiable
 
 from .. import _lib
 from ..options import options
-from ._runtime import *      # noqa: F401,F403
-from .layernorm import *      # noqa: F401,F403
+from ._runtime import (_account, _c, _dev, _gemm_key, _hidden_code_of, _hidden_empty, _hptr, _hrow_bytes, in_second_order_forward,
+                       _inputs_only, _is_h16, PackCache, _pair_hold, _pair_launches, _reduce_batch, _scratch, _wgrad_key,
+                       _workspace)
+from .layernorm import ln_residual
 
 
 def _wgrad_many(items, open_batch=True, pair_from=None):
@@ -100,11 +100,10 @@ def _wgrad(dy2, x2, want_bias, dy_mask=None, ws=None):
         return dyf.t().mm(xf), (dyf.sum(0) if want_bias else None)
     dw = torch.empty(N, K, dtype=torch.float32, device=dy2.device)
     db = torch.empty(N, dtype=torch.float32, device=dy2.device) if want_bias else None
-    with _dev(dy2):
-        if ws is None:
-            ws = _scratch(dy2, need, "wgrad")
-        _lib.check(lib.dg_linear_wgrad(_lib.ptr(dy2), _lib.ptr(dy_mask), _lib.ptr(x2), _lib.ptr(dw), _lib.ptr(db), ws.data_ptr(),
-                                       ws.numel(), R, N, K, _lib.dt(dy2), _lib.stream_of(dy2)), "dg_linear_wgrad")
+    if ws is None:
+        ws = _scratch(dy2, need, "wgrad")
+    _lib.launch("dg_linear_wgrad", dy2, _lib.ptr(dy2), _lib.ptr(dy_mask), _lib.ptr(x2), _lib.ptr(dw), _lib.ptr(db),
+                ws.data_ptr(), ws.numel(), R, N, K, _lib.dt(dy2))
     _pair_hold(dy2, dy_mask, x2, dw, db, ws)
     _account(_wgrad_key(R, N, K), dy2.element_size() * R * (N * (2 if dy_mask is not None else 1) + K), 2 * R * N * K)
     return dw, db
@@ -127,12 +126,11 @@ def _wgrad_h16(dy2, x2, want_bias, ws=None):
         raise RuntimeError(f"weight gradient with an fp16 hidden operand: float32 [R,128] partner expected, got {other.dtype} N={N} K={K}")
     dw = torch.empty(N, K, dtype=torch.float32, device=other.device)
     db = torch.empty(N, dtype=torch.float32, device=other.device) if want_bias else None
-    with _dev(other):
-        if ws is None:
-            ws = _scratch(other, int(lib.dg_linear_wgrad_workspace_bytes(R, N, K)), "wgrad")
-        code = _hidden_code_of(dy2 if _is_h16(dy2) else x2, R)
-        _lib.check(lib.dg_linear_wgrad(_hptr(dy2), None, _hptr(x2), _lib.ptr(dw), _lib.ptr(db), ws.data_ptr(), ws.numel(), R, N, K,
-                                       code, _lib.stream_of(other)), "dg_linear_wgrad")
+    if ws is None:
+        ws = _scratch(other, int(lib.dg_linear_wgrad_workspace_bytes(R, N, K)), "wgrad")
+    code = _hidden_code_of(dy2 if _is_h16(dy2) else x2, R)
+    _lib.launch("dg_linear_wgrad", other, _hptr(dy2), None, _hptr(x2), _lib.ptr(dw), _lib.ptr(db), ws.data_ptr(), ws.numel(),
+                R, N, K, code)
     _pair_hold(dy2, x2, dw, db, ws)
     _account(_wgrad_key(R, N, K), R * (4 * 128 + _hrow_bytes(_lib.F32_H16 if code == _lib.F32_H32 else code, 4, 384)), 2 * R * N * K)
     return dw, db
@@ -246,9 +244,7 @@ def packed_weight(w, mode: int, dtype=torch.float32):
         code = _lib.DTYPES[dtype]
         packed = torch.empty(int(lib.dg_row_gemm_packed_bytes(n_out, k, code)), dtype=torch.uint8, device=w.device)
         wd = _c(w.detach())
-        with _dev(w):
-            _lib.check(lib.dg_row_gemm_pack(_lib.fptr(wd), packed.data_ptr(), rows, cols, mode, code, _lib.stream_of(w)),
-                       "dg_row_gemm_pack")
+        _lib.launch("dg_row_gemm_pack", w, _lib.fptr(wd), packed.data_ptr(), rows, cols, mode, code)
         return packed
     return _pack_cache.get((w,), (mode, dtype), make)
 
@@ -262,9 +258,8 @@ def packed_weight3(w0, w1, w2, mode: int):
         n_out, k = (384, 128) if mode == 0 else (128, 384)
         packed = torch.empty(int(lib.dg_row_gemm_packed_bytes(n_out, k, 0)), dtype=torch.uint8, device=ws[0].device)
         wd = [_c(w.detach()) for w in ws]
-        with _dev(ws[0]):
-            _lib.check(lib.dg_row_gemm_pack3(_lib.fptr(wd[0]), _lib.fptr(wd[1]), _lib.fptr(wd[2]), packed.data_ptr(), 128, mode, 0,
-                                             _lib.stream_of(ws[0])), "dg_row_gemm_pack3")
+        _lib.launch("dg_row_gemm_pack3", ws[0], _lib.fptr(wd[0]), _lib.fptr(wd[1]), _lib.fptr(wd[2]), packed.data_ptr(), 128,
+                    mode, 0)
         return packed
     return _pack3_cache.get((w0, w1, w2), (mode,), make)
 
@@ -279,12 +274,9 @@ def lin3_supported(x2, ws) -> bool:
 def lin3(x2, ws, bs):
     """(x2 w0^T + b0, x2 w1^T + b1, x2 w2^T + b2) in one launch; ``bs`` entries may be None."""
     R = x2.shape[0]
-    lib = _lib.load()
     ys = [torch.empty(R, 128, dtype=x2.dtype, device=x2.device) for _ in range(3)]
-    with _dev(x2):
-        _lib.check(lib.dg_row_gemm_lin3(_lib.ptr(x2), packed_weight3(*ws, 0).data_ptr(), _lib.ptr(ys[0]), _lib.ptr(ys[1]),
-                                        _lib.ptr(ys[2]), R, _lib.fptr(bs[0]), _lib.fptr(bs[1]), _lib.fptr(bs[2]), 0,
-                                        _lib.stream_of(x2)), "dg_row_gemm_lin3")
+    _lib.launch("dg_row_gemm_lin3", x2, _lib.ptr(x2), packed_weight3(*ws, 0).data_ptr(), _lib.ptr(ys[0]), _lib.ptr(ys[1]),
+                _lib.ptr(ys[2]), R, _lib.fptr(bs[0]), _lib.fptr(bs[1]), _lib.fptr(bs[2]), 0)
     _account(_gemm_key(R, 128, 384), 4 * R * (128 + 384), 2 * R * 128 * 384)
     return ys
 
@@ -292,11 +284,9 @@ def lin3(x2, ws, bs):
 def sum3(a0, a1, a2, ws, residual=None):
     """a0 w0 + a1 w1 + a2 w2 (+ residual): the input gradient of three Linears that share their input, one launch."""
     R = a0.shape[0]
-    lib = _lib.load()
     y = torch.empty(R, 128, dtype=a0.dtype, device=a0.device)
-    with _dev(a0):
-        _lib.check(lib.dg_row_gemm_sum3(_lib.ptr(a0), _lib.ptr(a1), _lib.ptr(a2), packed_weight3(*ws, 1).data_ptr(), _lib.ptr(y),
-                                        R, _lib.ptr(residual), 0, _lib.stream_of(a0)), "dg_row_gemm_sum3")
+    _lib.launch("dg_row_gemm_sum3", a0, _lib.ptr(a0), _lib.ptr(a1), _lib.ptr(a2), packed_weight3(*ws, 1).data_ptr(),
+                _lib.ptr(y), R, _lib.ptr(residual), 0)
     _account(_gemm_key(R, 384, 128), 4 * R * (384 + 128 * (1 + (residual is not None))), 2 * R * 384 * 128)
     return y
 
@@ -307,11 +297,10 @@ def _wgrad3(dys, x2, want_bias, ws=None):
     lib = _lib.load()
     dw = torch.empty(384, 128, dtype=torch.float32, device=x2.device)
     db = torch.empty(384, dtype=torch.float32, device=x2.device) if want_bias else None
-    with _dev(x2):
-        if ws is None:
-            ws = _scratch(x2, int(lib.dg_linear_wgrad_workspace_bytes(R, 384, 128)), "wgrad")
-        _lib.check(lib.dg_linear_wgrad3(_lib.ptr(dys[0]), _lib.ptr(dys[1]), _lib.ptr(dys[2]), _lib.ptr(x2), _lib.ptr(dw),
-                                        _lib.ptr(db), ws.data_ptr(), ws.numel(), R, 0, _lib.stream_of(x2)), "dg_linear_wgrad3")
+    if ws is None:
+        ws = _scratch(x2, int(lib.dg_linear_wgrad_workspace_bytes(R, 384, 128)), "wgrad")
+    _lib.launch("dg_linear_wgrad3", x2, _lib.ptr(dys[0]), _lib.ptr(dys[1]), _lib.ptr(dys[2]), _lib.ptr(x2), _lib.ptr(dw),
+                _lib.ptr(db), ws.data_ptr(), ws.numel(), R, 0)
     _account(_wgrad_key(R, 384, 128), 4 * R * (384 + 128), 2 * R * 384 * 128)
     return dw, db
 
@@ -363,12 +352,9 @@ def _repack_entries(entries, dtype) -> int:
                 rows.append([ws[0].data_ptr(), packed.data_ptr(), 384, ws[0].shape[1], mode, ws[1].data_ptr(), ws[2].data_ptr()])
         tab = torch.tensor(rows, dtype=torch.int64, device=dev)
         _repack_tables[sig] = tab
-    lib = _lib.load()
     w0 = entries[0][2][0]
-    with _dev(w0):
-        _lib.check(lib.dg_row_gemm_pack_batch(tab.data_ptr(), len(entries),
-                                              max(384 if len(ws) == 3 else max(ws[0].shape) for _, _, ws, _, _ in entries),
-                                              _lib.DTYPES[dtype], _lib.stream_of(w0)), "dg_row_gemm_pack_batch")
+    _lib.launch("dg_row_gemm_pack_batch", w0, tab.data_ptr(), len(entries),
+                max(384 if len(ws) == 3 else max(ws[0].shape) for _, _, ws, _, _ in entries), _lib.DTYPES[dtype])
     for cache, key, _, _, _ in entries:
         cache.restamp(key)
     return len(entries)
@@ -410,12 +396,10 @@ def row_gemm(a2, packed, K, N, bias=None, relu=False, want_relu_bits=False, mask
         bits = torch.empty(int(lib.dg_row_gemm_mask_words(R, K, N, code)), dtype=torch.int32, device=dev)
     if residual is not None and residual.dtype != adt:
         residual = residual.to(adt)
-    with _dev(ref):
-        _lib.check(lib.dg_row_gemm(_hptr(a2), packed.data_ptr(), _hptr(y), R, K, N, _lib.fptr(bias),
-                                   1 if relu else 0, None if bits is None else bits.data_ptr(),
-                                   None if mask_bits is None else mask_bits.data_ptr(), _lib.ptr(residual),
-                                   _lib.fptr(gamma), _lib.fptr(beta), _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(pre),
-                                   float(eps), code, _lib.stream_of(ref)), "dg_row_gemm")
+    _lib.launch("dg_row_gemm", ref, _hptr(a2), packed.data_ptr(), _hptr(y), R, K, N, _lib.fptr(bias), 1 if relu else 0,
+                None if bits is None else bits.data_ptr(), None if mask_bits is None else mask_bits.data_ptr(),
+                _lib.ptr(residual), _lib.fptr(gamma), _lib.fptr(beta), _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(pre),
+                float(eps), code)
     _pair_hold(a2, packed, y, bias, bits, mask_bits, residual, gamma, beta, mean, rstd, pre)
     kb = _hrow_bytes(code, es, K) if K == 384 else es * K      # bytes per row of the A operand / of the result
     nb = _hrow_bytes(code, es, N) if N == 384 else es * N
@@ -457,15 +441,13 @@ def _ln_bwd_rows(pre, gamma, mean, rstd, dy2, dz_add=None, want_affine=True, bat
     dz = torch.empty_like(pre)
     dgamma, dbeta = (torch.empty(2, gamma.numel(), dtype=gamma.dtype, device=pre.device).unbind(0) if want_affine
                      else (None, None))
-    with _dev(pre):
-        if batch_slot is None:
-            ws, _ = _workspace(pre, R, N)
-        else:
-            ws = _scratch(pre, int(lib.dg_ln_workspace_bytes(R, N)), f"ln_batch{batch_slot}")
-        _lib.check(lib.dg_ln_residual_bwd_add(_lib.ptr(pre), None, _lib.fptr(_c(gamma)), _lib.ptr(mean),
-                                              _lib.ptr(rstd), _lib.ptr(dy2), _lib.ptr(dz_add), _lib.ptr(dz),
-                                              _lib.ptr(dgamma), _lib.ptr(dbeta), ws.data_ptr(), ws.numel(), R, N,
-                                              _lib.dt(pre), _lib.stream_of(pre)), "dg_ln_residual_bwd")
+    if batch_slot is None:
+        ws, _ = _workspace(pre, R, N)
+    else:
+        ws = _scratch(pre, int(lib.dg_ln_workspace_bytes(R, N)), f"ln_batch{batch_slot}")
+    _lib.launch("dg_ln_residual_bwd_add", pre, _lib.ptr(pre), None, _lib.fptr(_c(gamma)), _lib.ptr(mean), _lib.ptr(rstd),
+                _lib.ptr(dy2), _lib.ptr(dz_add), _lib.ptr(dz), _lib.ptr(dgamma), _lib.ptr(dbeta), ws.data_ptr(), ws.numel(),
+                R, N, _lib.dt(pre))
     _account("ln_bwd", pre.element_size() * R * N * (4 if dz_add is not None else 3))
     return dz, dgamma, dbeta
 
@@ -483,12 +465,10 @@ def row_gemm_ln_bwd(a2, packed, K, residual, pre, gamma, mean, rstd):
     dz = torch.empty(R, 128, dtype=a2.dtype, device=a2.device)
     dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
     code = _lib.dt(a2)
-    with _dev(a2):
-        ws = _scratch(a2, int(lib.dg_row_gemm_ln_bwd_workspace_bytes(code)), "lnb")
-        _lib.check(lib.dg_row_gemm_ln_bwd(_lib.ptr(a2), packed.data_ptr(), _lib.ptr(dz), R, K, _lib.ptr(residual),
-                                          _lib.ptr(pre), _lib.ptr(mean), _lib.ptr(rstd), _lib.fptr(_c(gamma)),
-                                          _lib.ptr(dgamma), _lib.ptr(dbeta), ws.data_ptr(), ws.numel(), code,
-                                          _lib.stream_of(a2)), "dg_row_gemm_ln_bwd")
+    ws = _scratch(a2, int(lib.dg_row_gemm_ln_bwd_workspace_bytes(code)), "lnb")
+    _lib.launch("dg_row_gemm_ln_bwd", a2, _lib.ptr(a2), packed.data_ptr(), _lib.ptr(dz), R, K, _lib.ptr(residual),
+                _lib.ptr(pre), _lib.ptr(mean), _lib.ptr(rstd), _lib.fptr(_c(gamma)), _lib.ptr(dgamma), _lib.ptr(dbeta),
+                ws.data_ptr(), ws.numel(), code)
     _account(_gemm_key(R, K, 128), a2.element_size() * R * (K + 128 * (2 + (residual is not None))), 2 * R * K * 128)
     return dz, dgamma, dbeta
 
@@ -509,13 +489,11 @@ def ln_bwd_row_gemm(pre, gamma, mean, rstd, dy2, packed, want_affine=True, batch
     dgamma, dbeta = (torch.empty(2, gamma.numel(), dtype=gamma.dtype, device=pre.device).unbind(0) if want_affine
                      else (None, None))
     code = _lib.dt(pre)
-    with _dev(pre):
-        ws = _scratch(pre, int(lib.dg_row_gemm_ln_bwd_workspace_bytes(code)),
-                      "lna" if batch_slot is None else f"lna_batch{batch_slot}")
-        _lib.check(lib.dg_row_gemm_ln_bwd_in(_lib.ptr(dy2), _lib.ptr(pre), _lib.ptr(mean), _lib.ptr(rstd),
-                                             _lib.fptr(_c(gamma)), packed.data_ptr(), _lib.ptr(dz), _lib.ptr(y),
-                                             _lib.ptr(dgamma), _lib.ptr(dbeta), ws.data_ptr(), ws.numel(), R, 128, 128,
-                                             code, _lib.stream_of(pre)), "dg_row_gemm_ln_bwd_in")
+    ws = _scratch(pre, int(lib.dg_row_gemm_ln_bwd_workspace_bytes(code)),
+                  "lna" if batch_slot is None else f"lna_batch{batch_slot}")
+    _lib.launch("dg_row_gemm_ln_bwd_in", pre, _lib.ptr(dy2), _lib.ptr(pre), _lib.ptr(mean), _lib.ptr(rstd),
+                _lib.fptr(_c(gamma)), packed.data_ptr(), _lib.ptr(dz), _lib.ptr(y), _lib.ptr(dgamma), _lib.ptr(dbeta),
+                ws.data_ptr(), ws.numel(), R, 128, 128, code)
     _account(_gemm_key(R, 128, 128), pre.element_size() * R * 128 * 4, 2 * R * 128 * 128)
     return dz, y, dgamma, dbeta
 
@@ -523,15 +501,12 @@ def ln_bwd_row_gemm(pre, gamma, mean, rstd, dy2, packed, want_affine=True, batch
 def _ln_bwd2_rows(pre, gamma, mean, rstd, dy2, tz):
     """Backward of ``_ln_bwd_rows`` w.r.t. the adjoint ``tz`` of dz -> (gz, gdy, ggamma)."""
     R, N = pre.shape
-    lib = _lib.load()
     gz, gdy = torch.empty_like(pre), torch.empty_like(pre)
     ggamma = torch.empty_like(gamma)
-    with _dev(pre):
-        ws, _ = _workspace(pre, R, N)
-        _lib.check(lib.dg_ln_residual_bwd2(_lib.ptr(pre), None, _lib.fptr(_c(gamma)), _lib.ptr(mean), _lib.ptr(rstd),
-                                           _lib.ptr(dy2), _lib.ptr(tz), _lib.ptr(gz), _lib.ptr(gdy), _lib.ptr(ggamma),
-                                           ws.data_ptr(), ws.numel(), R, N, _lib.dt(pre), _lib.stream_of(pre)),
-                   "dg_ln_residual_bwd2")
+    ws, _ = _workspace(pre, R, N)
+    _lib.launch("dg_ln_residual_bwd2", pre, _lib.ptr(pre), None, _lib.fptr(_c(gamma)), _lib.ptr(mean), _lib.ptr(rstd),
+                _lib.ptr(dy2), _lib.ptr(tz), _lib.ptr(gz), _lib.ptr(gdy), _lib.ptr(ggamma), ws.data_ptr(), ws.numel(), R, N,
+                _lib.dt(pre))
     _account("ln_bwd2", pre.element_size() * R * N * 5)
     return gz, gdy, ggamma
 
@@ -581,6 +556,3 @@ def linear_ln(x, weight, bias, residual, gamma, beta, eps: float = 1e-5):
     if not _fusable(x, weight) or tuple(weight.shape) != (128, 128) or bias is None or in_second_order_forward():
         return _composite_linear_ln(x, weight, bias, residual, gamma, beta, float(eps))
     return _LinearLN.apply(x, weight, bias, residual, gamma, beta, float(eps))
-
-
-__all__ = [_n for _n in dir() if not _n.startswith("__")]

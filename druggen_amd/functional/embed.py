@@ -2,22 +2,14 @@
 table) and the output slots that let several producers write one tensor."""
 from __future__ import annotations
 
-import contextlib
-import ctypes
-import threading
-
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from .. import _lib
 from ..options import options
-from ._runtime import *      # noqa: F401,F403
-from .layernorm import *      # noqa: F401,F403
-from .dense import *      # noqa: F401,F403
-from .heads import *      # noqa: F401,F403
-from .ffn import *      # noqa: F401,F403
-from .attention import *      # noqa: F401,F403
+from ._runtime import _account, _c, in_second_order_forward, _inputs_only, PackCache, _scratch
+from .dense import _double_backward_fallback, linear
 
 
 # --------------------------------------------------------------------------
@@ -39,9 +31,7 @@ def _embed_packed_w2(w2, dgrad: bool = False):
         n_floats = lib.dg_embed_sym_dgrad_packed_floats() if dgrad else lib.dg_embed_sym_packed_floats()
         packed = torch.empty(int(n_floats), dtype=torch.float32, device=w2.device)
         wd = _c(w2.detach())
-        with _dev(w2):
-            pack = lib.dg_embed_sym_pack_dgrad if dgrad else lib.dg_embed_sym_pack
-            _lib.check(pack(_lib.ptr(wd), _lib.ptr(packed), _lib.stream_of(w2)), "dg_embed_sym_pack")
+        _lib.launch("dg_embed_sym_pack_dgrad" if dgrad else "dg_embed_sym_pack", w2, _lib.ptr(wd), _lib.ptr(packed))
         return packed
     return _embed_pack_cache.get((w2,), (dgrad,), make)
 
@@ -105,12 +95,10 @@ class _EmbedSym(Function):
         a = _c(a)
         B, N, _, E = a.shape
         H, C = w1.shape[0], w2.shape[0]
-        lib = _lib.load()
         out = _take_slot(slot, (B, N, N, C), out_dtype, a.device)
-        with _dev(a):
-            _lib.check(lib.dg_embed_sym_fwd(_lib.fptr(a), _lib.fptr(_c(w1)), _lib.fptr(_c(b1)), _lib.fptr(_embed_packed_w2(w2)),
-                                            _lib.fptr(_c(b2)), _lib.ptr(out), B, N, E, H, C, _ACT_IDS[act],
-                                            _lib.dt(out), _lib.stream_of(a)), "dg_embed_sym_fwd")
+        _lib.launch("dg_embed_sym_fwd", a, _lib.fptr(a), _lib.fptr(_c(w1)), _lib.fptr(_c(b1)),
+                    _lib.fptr(_embed_packed_w2(w2)), _lib.fptr(_c(b2)), _lib.ptr(out), B, N, E, H, C, _ACT_IDS[act],
+                    _lib.dt(out))
         _account("embed_sym", B * N * N * (4 * E + out.element_size() * C), 2 * B * N * N * (E * H + H * C))
         ctx.save_for_backward(a, w1, b1, w2, b2)
         ctx.act = act
@@ -146,25 +134,21 @@ def _embed_bwd_launch(a, w1, b1, w2, b2, g, act, out_dtype, need_da, need_w):
             and options.embed_bf16 == "fast"):
         # bf16 gradients, relu / leaky: row-block streaming kernel (csrc/embed_bf16.hip)
         need = int(lib.dg_embed_sym_bwd_bf16_workspace_bytes(B, N))
-        with _dev(a):
-            ws = _scratch(a, need, "embed16")
-            _lib.check(lib.dg_embed_sym_bwd_bf16(_lib.fptr(a), _lib.fptr(_c(w1)), _lib.fptr(_c(b1)), _lib.fptr(_c(w2)),
-                                                 _lib.fptr(_c(b2)), _lib.ptr(g), _lib.ptr(da), _lib.ptr(dw1), _lib.ptr(db1),
-                                                 _lib.ptr(dw2), _lib.ptr(db2), ws.data_ptr(), ws.numel(), B, N, E, H, C,
-                                                 _ACT_IDS[act], _lib.stream_of(a)), "dg_embed_sym_bwd_bf16")
+        ws = _scratch(a, need, "embed16")
+        _lib.launch("dg_embed_sym_bwd_bf16", a, _lib.fptr(a), _lib.fptr(_c(w1)), _lib.fptr(_c(b1)), _lib.fptr(_c(w2)),
+                    _lib.fptr(_c(b2)), _lib.ptr(g), _lib.ptr(da), _lib.ptr(dw1), _lib.ptr(db1), _lib.ptr(dw2), _lib.ptr(db2),
+                    ws.data_ptr(), ws.numel(), B, N, E, H, C, _ACT_IDS[act])
         _account("embed_sym", B * N * N * (4 * E * (2 if da is not None else 1) + 2 * g.element_size() * C),
                  2 * B * N * N * (E * H + H * C) * 3)
         if not need_w:
             dw1 = db1 = dw2 = db2 = None
         return da, dw1, db1, dw2, db2
     need = int(lib.dg_embed_sym_workspace_bytes(B, N))
-    with _dev(a):
-        ws = _scratch(a, need, "embed")
-        _lib.check(lib.dg_embed_sym_bwd(_lib.fptr(a), _lib.fptr(_c(w1)), _lib.fptr(_c(b1)),
-                                        _lib.fptr(_embed_packed_w2(w2)), _lib.fptr(_embed_packed_w2(w2, True)),
-                                        _lib.fptr(_c(b2)), _lib.ptr(g), _lib.ptr(da), _lib.ptr(dw1), _lib.ptr(db1),
-                                        _lib.ptr(dw2), _lib.ptr(db2), ws.data_ptr(), ws.numel(), B, N, E, H, C,
-                                        _ACT_IDS[act], _lib.dt(g), _lib.stream_of(a)), "dg_embed_sym_bwd")
+    ws = _scratch(a, need, "embed")
+    _lib.launch("dg_embed_sym_bwd", a, _lib.fptr(a), _lib.fptr(_c(w1)), _lib.fptr(_c(b1)), _lib.fptr(_embed_packed_w2(w2)),
+                _lib.fptr(_embed_packed_w2(w2, True)), _lib.fptr(_c(b2)), _lib.ptr(g), _lib.ptr(da), _lib.ptr(dw1),
+                _lib.ptr(db1), _lib.ptr(dw2), _lib.ptr(db2), ws.data_ptr(), ws.numel(), B, N, E, H, C, _ACT_IDS[act],
+                _lib.dt(g))
     _account("embed_sym", B * N * N * (4 * E * (2 if da is not None else 1) + g.element_size() * C),
              2 * B * N * N * (E * H + H * C) * 3)
     if not need_w:
@@ -200,13 +184,11 @@ class _EmbedSymBwd(Function):
         gg = torch.empty_like(g)
         gw1, gw2 = torch.empty_like(w1), torch.empty_like(w2)
         need = int(lib.dg_embed_sym_workspace_bytes(B, N))
-        with _dev(a):
-            ws = _scratch(a, need, "embed")
-            _lib.check(lib.dg_embed_sym_bwd2(_lib.fptr(_c(a)), _lib.fptr(_c(w1)), _lib.fptr(_c(b1)),
-                                             _lib.fptr(_embed_packed_w2(w2)), _lib.fptr(_embed_packed_w2(w2, True)),
-                                             _lib.fptr(_c(b2)), _lib.ptr(g), _lib.fptr(t), _lib.ptr(gg), _lib.ptr(gw1),
-                                             _lib.ptr(gw2), ws.data_ptr(), ws.numel(), B, N, E, H, C,
-                                             _ACT_IDS[ctx.act], _lib.dt(g), _lib.stream_of(a)), "dg_embed_sym_bwd2")
+        ws = _scratch(a, need, "embed")
+        _lib.launch("dg_embed_sym_bwd2", a, _lib.fptr(_c(a)), _lib.fptr(_c(w1)), _lib.fptr(_c(b1)),
+                    _lib.fptr(_embed_packed_w2(w2)), _lib.fptr(_embed_packed_w2(w2, True)), _lib.fptr(_c(b2)), _lib.ptr(g),
+                    _lib.fptr(t), _lib.ptr(gg), _lib.ptr(gw1), _lib.ptr(gw2), ws.data_ptr(), ws.numel(), B, N, E, H, C,
+                    _ACT_IDS[ctx.act], _lib.dt(g))
         _account("embed_sym", B * N * N * (8 * E + 2 * g.element_size() * C), 2 * B * N * N * (E * H + H * C) * 4)
         if _inputs_only() or not ctx.needs_input_grad[1]:
             gw1 = gw2 = None
@@ -280,12 +262,11 @@ class _OneHotEmbed(Function):
     def forward(ctx, labels, table, out_dtype, slot=None):
         B, N = labels.shape[0], labels.shape[1]
         E, C = table.shape
-        lib = _lib.load()
         table = _c(table)
         out = _take_slot(slot, (B, N, N, C), out_dtype, labels.device)
-        with _dev(labels):
-            _lib.check(lib.dg_onehot_embed_fwd(labels.data_ptr(), _lib.fptr(table), _lib.ptr(out), B, N, E, C, _lib.dt(out),
-                                               _lib.stream_of(out)), "dg_onehot_embed_fwd")
+        # (labels and out live on one device: the stream is looked up by device index)
+        _lib.launch("dg_onehot_embed_fwd", labels, labels.data_ptr(), _lib.fptr(table), _lib.ptr(out), B, N, E, C,
+                    _lib.dt(out))
         _account("embed_sym", B * N * N * (8 + out.element_size() * C))
         ctx.save_for_backward(labels)
         ctx.shape = (E, C, out_dtype)
@@ -301,10 +282,9 @@ class _OneHotEmbed(Function):
         g = _c(g if g.dtype == out_dtype else g.to(out_dtype))
         dtable = torch.empty(E, C, dtype=torch.float32, device=g.device)
         need = int(lib.dg_onehot_embed_workspace_bytes(E, C))
-        with _dev(g):
-            ws = _scratch(g, need, "onehot")
-            _lib.check(lib.dg_onehot_embed_bwd(labels.data_ptr(), _lib.ptr(g), _lib.ptr(dtable), ws.data_ptr(), ws.numel(),
-                                               B, N, E, C, _lib.dt(g), _lib.stream_of(g)), "dg_onehot_embed_bwd")
+        ws = _scratch(g, need, "onehot")
+        _lib.launch("dg_onehot_embed_bwd", g, labels.data_ptr(), _lib.ptr(g), _lib.ptr(dtable), ws.data_ptr(), ws.numel(), B,
+                    N, E, C, _lib.dt(g))
         _account("embed_sym", B * N * N * (8 + g.element_size() * C))
         return None, dtable, None, None
 
@@ -315,6 +295,3 @@ def embed_sym_onehot(labels, w1, b1, w2, b2, act: str, out_dtype=torch.float32, 
     f = _ACT_FNS[act]
     table = f(torch.nn.functional.linear(f(w1.t() + b1), w2, b2))      # [E, dim]: row c = f(one_hot(c))
     return _OneHotEmbed.apply(labels, table, out_dtype, slot)
-
-
-__all__ = [_n for _n in dir() if not _n.startswith("__")]

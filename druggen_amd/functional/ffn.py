@@ -2,9 +2,7 @@
 one autograd node -- float32 (fused forward kernel or two row GEMMs, node + edge halves riding in one launch) and bf16."""
 from __future__ import annotations
 
-import contextlib
 import ctypes
-import threading
 
 import torch
 from torch.autograd import Function
@@ -12,10 +10,11 @@ from torch.autograd.function import once_differentiable
 
 from .. import _lib
 from ..options import options
-from ._runtime import *      # noqa: F401,F403
-from .layernorm import *      # noqa: F401,F403
-from .dense import *      # noqa: F401,F403
-from .heads import *      # noqa: F401,F403
+from ._runtime import (_account, _alias_outputs_enabled, _c, _ffn_bwd_codes, _gemm_key, _hidden_code, _hidden_code_of,
+                       _hidden_empty, hidden_storage, _hptr, _hrow_bytes, in_second_order_forward, _inputs_only, _is_h16,
+                       _long_rows, PackCache, _pair_launches, _scratch, _weight_alias, _wgrad_key)
+from .layernorm import ln_residual
+from .dense import _double_backward_fallback, _join_alias_grads, linear, _ln_bwd2_rows, packed_weight, row_gemm, _wgrad_many
 
 
 def _fused_ffn_enabled() -> bool:
@@ -36,9 +35,7 @@ def _ffn_packed_f32(w1, w2):
     def make(w1, w2):
         lib = _lib.load()
         packed = torch.empty(int(lib.dg_ffn_f32_packed_bytes()), dtype=torch.uint8, device=w1.device)
-        with _dev(w1):
-            _lib.check(lib.dg_ffn_f32_pack(_lib.fptr(_c(w1.detach())), _lib.fptr(_c(w2.detach())), packed.data_ptr(),
-                                           _lib.stream_of(w1)), "dg_ffn_f32_pack")
+        _lib.launch("dg_ffn_f32_pack", w1, _lib.fptr(_c(w1.detach())), _lib.fptr(_c(w2.detach())), packed.data_ptr())
         return packed
     return _ffn_f32_pack_cache.get((w1, w2), (), make)
 
@@ -118,23 +115,18 @@ def _ffn_fwd_account(p, fused, keep):
 
 def _ffn_fwd(branches, keep):
     """Forward of one or two feed-forward problems (``_ffn_fwd_problems``) in one call of the library; returns the problems."""
-    lib = _lib.load()
     probs, fused = _ffn_fwd_problems(branches, keep)
     p0 = probs[0]
     ref = p0["x2"]
     ptrs = [_ffn_fwd_pointers(p, fused) for p in probs]
-    with _dev(ref):
-        if fused or len(probs) == 2:
-            cargs = [ctypes.byref(_lib.FFNFwdArgs(*f, p["R"], float(p["eps"]))) for f, p in zip(ptrs, probs)]
-        if fused:      # ONE launch: the node rows ride in the launch over the edge rows, the hidden tensors stay on chip
-            _lib.check(lib.dg_ffn_ln_fwd_f32(cargs[0] if len(probs) == 2 else None, cargs[-1], _lib.stream_of(ref)),
-                       "dg_ffn_ln_fwd_f32")
-        elif len(probs) == 1:      # two row-GEMM launches (bias + ReLU epilogue; bias + residual + LayerNorm epilogue)
-            _lib.check(lib.dg_edge_ffn_ln_fwd(*ptrs[0], p0["R"], p0["C"], p0["H"], p0["eps"], p0["code"], _lib.stream_of(ref)),
-                       "dg_edge_ffn_ln_fwd")
-        else:          # one call: node, edge, node, edge inside dg_launch_pair_begin / _end
-            _lib.check(lib.dg_edge_ffn_ln_fwd_pair(*cargs, p0["C"], p0["H"], p0["code"], _lib.stream_of(ref)),
-                       "dg_edge_ffn_ln_fwd_pair")
+    if fused or len(probs) == 2:
+        cargs = [ctypes.byref(_lib.FFNFwdArgs(*f, p["R"], float(p["eps"]))) for f, p in zip(ptrs, probs)]
+    if fused:      # ONE launch: the node rows ride in the launch over the edge rows, the hidden tensors stay on chip
+        _lib.launch("dg_ffn_ln_fwd_f32", ref, cargs[0] if len(probs) == 2 else None, cargs[-1])
+    elif len(probs) == 1:      # two row-GEMM launches (bias + ReLU epilogue; bias + residual + LayerNorm epilogue)
+        _lib.launch("dg_edge_ffn_ln_fwd", ref, *ptrs[0], p0["R"], p0["C"], p0["H"], p0["eps"], p0["code"])
+    else:          # one call: node, edge, node, edge inside dg_launch_pair_begin / _end
+        _lib.launch("dg_edge_ffn_ln_fwd_pair", ref, *cargs, p0["C"], p0["H"], p0["code"])
     for p in probs:
         _ffn_fwd_account(p, fused, keep)
     return probs
@@ -201,33 +193,32 @@ def _ffn_bwd(ctx, args):
     adt, dev = ref.dtype, ref.device
     code, dh_code = _ffn_bwd_codes(p0["h"], adt, p0["R"], p0["H"])
     cargs = []
-    with _dev(ref):
-        for i, p in enumerate(probs):      # dg_ffn_bwd_args: outputs and a workspace of its own per problem
-            R, C, H = p["R"], p["C"], p["H"]
-            p["dgamma"] = p["dbeta"] = None
-            if p["dy2"] is not None:
-                p["dz"] = torch.empty(R, C, dtype=adt, device=dev)
-                if p["want_aff"]:      # adjacent in memory: their reduction joins the call's single reduce launch
-                    p["dgamma"], p["dbeta"] = torch.empty(2, p["gamma"].numel(), dtype=p["gamma"].dtype, device=dev).unbind(0)
-            p["dh"] = _hidden_empty(R, H, adt, dh_code, dev)
-            p["dx"] = torch.empty(R, C, dtype=adt, device=dev) if p["want_x"] else None
-            p["dw1"] = p["db1"] = p["dw2"] = p["db2"] = None
-            if p["want_w"]:
-                p["dw1"], p["dw2"] = torch.empty_like(p["w1"]), torch.empty_like(p["w2"])
-                p["db1"] = torch.empty(H, dtype=torch.float32, device=dev)
-                p["db2"] = torch.empty(C, dtype=torch.float32, device=dev)
-            ws = _scratch(ref, int(lib.dg_edge_ffn_ln_workspace_bytes(R, C, H)), "ffn" if len(probs) == 1 else f"ffn_pair{i}")
-            cargs.append((
-                _lib.ptr(p["x2"]), _hptr(p["h"]), p["bits"].data_ptr(), _lib.ptr(p["pre"]), _lib.ptr(p["mean"]),
-                _lib.ptr(p["rstd"]), _lib.fptr(_c(p["gamma"])), packed_weight(p["w1"], 1, adt).data_ptr(),
-                packed_weight(p["w2"], 1, adt).data_ptr(), _lib.ptr(p["dy2"]), _lib.ptr(p["dz_add"]), _lib.ptr(p["dz"]),
-                _hptr(p["dh"]), _lib.ptr(p["dx"]), _lib.ptr(p["dgamma"]), _lib.ptr(p["dbeta"]), _lib.ptr(p["dw1"]),
-                _lib.ptr(p["db1"]), _lib.ptr(p["dw2"]), _lib.ptr(p["db2"]), ws.data_ptr(), ws.numel(), R))
-        if len(probs) == 1:
-            _lib.check(lib.dg_edge_ffn_ln_bwd(*cargs[0], p0["C"], p0["H"], code, _lib.stream_of(ref)), "dg_edge_ffn_ln_bwd")
-        else:
-            _lib.check(lib.dg_edge_ffn_ln_bwd_pair(*(ctypes.byref(_lib.FFNBwdArgs(*c)) for c in cargs), p0["C"], p0["H"], code,
-                                                   _lib.stream_of(ref)), "dg_edge_ffn_ln_bwd_pair")
+    for i, p in enumerate(probs):      # dg_ffn_bwd_args: outputs and a workspace of its own per problem
+        R, C, H = p["R"], p["C"], p["H"]
+        p["dgamma"] = p["dbeta"] = None
+        if p["dy2"] is not None:
+            p["dz"] = torch.empty(R, C, dtype=adt, device=dev)
+            if p["want_aff"]:      # adjacent in memory: their reduction joins the call's single reduce launch
+                p["dgamma"], p["dbeta"] = torch.empty(2, p["gamma"].numel(), dtype=p["gamma"].dtype, device=dev).unbind(0)
+        p["dh"] = _hidden_empty(R, H, adt, dh_code, dev)
+        p["dx"] = torch.empty(R, C, dtype=adt, device=dev) if p["want_x"] else None
+        p["dw1"] = p["db1"] = p["dw2"] = p["db2"] = None
+        if p["want_w"]:
+            p["dw1"], p["dw2"] = torch.empty_like(p["w1"]), torch.empty_like(p["w2"])
+            p["db1"] = torch.empty(H, dtype=torch.float32, device=dev)
+            p["db2"] = torch.empty(C, dtype=torch.float32, device=dev)
+        ws = _scratch(ref, int(lib.dg_edge_ffn_ln_workspace_bytes(R, C, H)), "ffn" if len(probs) == 1 else f"ffn_pair{i}")
+        cargs.append((
+            _lib.ptr(p["x2"]), _hptr(p["h"]), p["bits"].data_ptr(), _lib.ptr(p["pre"]), _lib.ptr(p["mean"]),
+            _lib.ptr(p["rstd"]), _lib.fptr(_c(p["gamma"])), packed_weight(p["w1"], 1, adt).data_ptr(),
+            packed_weight(p["w2"], 1, adt).data_ptr(), _lib.ptr(p["dy2"]), _lib.ptr(p["dz_add"]), _lib.ptr(p["dz"]),
+            _hptr(p["dh"]), _lib.ptr(p["dx"]), _lib.ptr(p["dgamma"]), _lib.ptr(p["dbeta"]), _lib.ptr(p["dw1"]),
+            _lib.ptr(p["db1"]), _lib.ptr(p["dw2"]), _lib.ptr(p["db2"]), ws.data_ptr(), ws.numel(), R))
+    if len(probs) == 1:
+        _lib.launch("dg_edge_ffn_ln_bwd", ref, *cargs[0], p0["C"], p0["H"], code)
+    else:
+        _lib.launch("dg_edge_ffn_ln_bwd_pair", ref, *(ctypes.byref(_lib.FFNBwdArgs(*c)) for c in cargs), p0["C"], p0["H"],
+                    code)
     saved, outs = [], []
     for p in probs:
         _ffn_bwd_account(p, code, dh_code)
@@ -422,9 +413,7 @@ def _ffn_packed_bf16(w1, w2):
     def make(w1, w2):
         lib = _lib.load()
         packed = torch.empty(int(lib.dg_ffn_bf16_packed_bytes()), dtype=torch.uint8, device=w1.device)
-        with _dev(w1):
-            _lib.check(lib.dg_ffn_bf16_pack(_lib.fptr(_c(w1.detach())), _lib.fptr(_c(w2.detach())), packed.data_ptr(),
-                                            _lib.stream_of(w1)), "dg_ffn_bf16_pack")
+        _lib.launch("dg_ffn_bf16_pack", w1, _lib.fptr(_c(w1.detach())), _lib.fptr(_c(w2.detach())), packed.data_ptr())
         return packed
     return _ffn_pack_cache.get((w1, w2), (), make)
 
@@ -449,12 +438,9 @@ class _FFNLNFusedBF16(Function):
         rstd = torch.empty(Rp, dtype=torch.float32, device=dev)[:R]
         pre = torch.empty(Rp, C, dtype=torch.bfloat16, device=dev)[:R] if record else None
         bits = torch.empty(int(lib.dg_ffn_bf16_mask_words(R)), dtype=torch.int32, device=dev) if record else None
-        with _dev(x2):
-            _lib.check(lib.dg_ffn_ln_fwd_bf16(_lib.ptr(x2), _ffn_packed_bf16(w1, w2).data_ptr(), _lib.fptr(_c(b1)),
-                                              _lib.fptr(_c(b2)), _lib.fptr(_c(gamma)), _lib.fptr(_c(beta)), _lib.ptr(y),
-                                              _lib.ptr(pre), _lib.ptr(mean), _lib.ptr(rstd),
-                                              None if bits is None else bits.data_ptr(), R, eps, _lib.stream_of(x2)),
-                       "dg_ffn_ln_fwd_bf16")
+        _lib.launch("dg_ffn_ln_fwd_bf16", x2, _lib.ptr(x2), _ffn_packed_bf16(w1, w2).data_ptr(), _lib.fptr(_c(b1)),
+                    _lib.fptr(_c(b2)), _lib.fptr(_c(gamma)), _lib.fptr(_c(beta)), _lib.ptr(y), _lib.ptr(pre), _lib.ptr(mean),
+                    _lib.ptr(rstd), None if bits is None else bits.data_ptr(), R, eps)
         _account("ffn" if R >= _lib.edge_rows() else "ffn_node", 2 * R * C * (3 if record else 2) + (48 * R if record else 0), 4 * R * C * 3 * C,
                  floor=2 * R * C * 2)
         if record:
@@ -486,14 +472,11 @@ class _FFNLNFusedBF16(Function):
             dw2, db2 = torch.empty_like(w2), torch.empty(C, dtype=torch.float32, device=dev)
             bits2 = torch.empty_like(bits)
         need = int(lib.dg_ffn_bf16_workspace_bytes(R))
-        with _dev(x2):
-            ws = _scratch(x2, need, "ffn16")
-            _lib.check(lib.dg_ffn_ln_bwd_bf16(_lib.ptr(x2), _lib.ptr(pre), _lib.ptr(mean), _lib.ptr(rstd), bits.data_ptr(),
-                                              _lib.fptr(_c(gamma)), _ffn_packed_bf16(w1, w2).data_ptr(), _lib.fptr(_c(b1)),
-                                              _lib.ptr(dy2), _lib.ptr(dz), _lib.ptr(dx), _lib.ptr(dgamma), _lib.ptr(dbeta),
-                                              _lib.ptr(dw1), _lib.ptr(db1), _lib.ptr(dw2), _lib.ptr(db2),
-                                              None if bits2 is None else bits2.data_ptr(), ws.data_ptr(), ws.numel(), R,
-                                              _lib.stream_of(x2)), "dg_ffn_ln_bwd_bf16")
+        ws = _scratch(x2, need, "ffn16")
+        _lib.launch("dg_ffn_ln_bwd_bf16", x2, _lib.ptr(x2), _lib.ptr(pre), _lib.ptr(mean), _lib.ptr(rstd), bits.data_ptr(),
+                    _lib.fptr(_c(gamma)), _ffn_packed_bf16(w1, w2).data_ptr(), _lib.fptr(_c(b1)), _lib.ptr(dy2), _lib.ptr(dz),
+                    _lib.ptr(dx), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(dw1), _lib.ptr(db1), _lib.ptr(dw2),
+                    _lib.ptr(db2), None if bits2 is None else bits2.data_ptr(), ws.data_ptr(), ws.numel(), R)
         lvl = "" if R >= _lib.edge_rows() else "_node"
         _account("ffn" + lvl, 2 * R * C * (4 if want_x else 3) + 48 * R, 4 * R * C * H if want_x else 2 * R * C * H)
         if want_w:
@@ -530,6 +513,3 @@ def ffn_ln(x, w1, b1, w2, b2, gamma, beta, eps: float = 1e-5, want_handle: bool 
         if want_handle and x.dtype == torch.float32 and pre is not None and pre.requires_grad:
             handle = LNHandle(pre, mean, rstd, gamma, beta)
     return (y, handle) if want_handle else y
-
-
-__all__ = [_n for _n in dir() if not _n.startswith("__")]

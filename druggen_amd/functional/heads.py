@@ -2,20 +2,13 @@
 (reference src/model/models.py:63-66,95-101,165-171,200-207)."""
 from __future__ import annotations
 
-import contextlib
-import ctypes
-import threading
-import weakref
-
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from .. import _lib
-from ..options import options
-from ._runtime import *      # noqa: F401,F403
-from .layernorm import *      # noqa: F401,F403
-from .dense import *      # noqa: F401,F403
+from ._runtime import _account, _c, _inputs_only, _scratch
+from .dense import _double_backward_fallback, linear, _wgrad
 
 
 class _Readout(Function):
@@ -30,11 +23,8 @@ class _Readout(Function):
         x2 = _c(x).reshape(-1, K)
         R = x2.shape[0]
         y = torch.empty(R, N, dtype=torch.float32, device=x.device)
-        lib = _lib.load()
-        with _dev(x2):
-            _lib.check(lib.dg_skinny_linear_fwd(_lib.ptr(x2), _lib.fptr(_c(w)), _lib.fptr(None if b is None else _c(b)),
-                                                _lib.ptr(y), R, N, K, _lib.dt(x2), _lib.stream_of(x2)),
-                       "dg_skinny_linear_fwd")
+        _lib.launch("dg_skinny_linear_fwd", x2, _lib.ptr(x2), _lib.fptr(_c(w)), _lib.fptr(None if b is None else _c(b)),
+                    _lib.ptr(y), R, N, K, _lib.dt(x2))
         _account("readout", x2.element_size() * R * K + 4 * R * N)
         ctx.save_for_backward(x, w, b)
         return y.view(*x.shape[:-1], N)
@@ -51,20 +41,17 @@ class _Readout(Function):
         x2 = _c(x).reshape(-1, K)
         R = x2.shape[0]
         dx = dw = db = None
-        with _dev(x2):
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x2)
-                _lib.check(lib.dg_skinny_linear_dgrad(_lib.ptr(dy2), _lib.fptr(_c(w)), _lib.ptr(dx), R, N, K, _lib.dt(x2),
-                                                      _lib.stream_of(x2)), "dg_skinny_linear_dgrad")
-                _account("readout", x2.element_size() * R * K + 4 * R * N)
-            if ctx.needs_input_grad[1] and not _inputs_only():
-                dw = torch.empty_like(w)
-                db = torch.empty(N, dtype=torch.float32, device=x.device) if b is not None else None
-                ws = _scratch(x2, int(lib.dg_linear_wgrad_workspace_bytes(R, N, K)), "wgrad")
-                _lib.check(lib.dg_skinny_linear_wgrad(_lib.ptr(dy2), _lib.ptr(x2), _lib.ptr(dw), _lib.ptr(db), ws.data_ptr(),
-                                                      ws.numel(), R, N, K, _lib.dt(x2), _lib.stream_of(x2)),
-                           "dg_skinny_linear_wgrad")
-                _account("linear_wgrad", x2.element_size() * R * K + 4 * R * N)
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x2)
+            _lib.launch("dg_skinny_linear_dgrad", x2, _lib.ptr(dy2), _lib.fptr(_c(w)), _lib.ptr(dx), R, N, K, _lib.dt(x2))
+            _account("readout", x2.element_size() * R * K + 4 * R * N)
+        if ctx.needs_input_grad[1] and not _inputs_only():
+            dw = torch.empty_like(w)
+            db = torch.empty(N, dtype=torch.float32, device=x.device) if b is not None else None
+            ws = _scratch(x2, int(lib.dg_linear_wgrad_workspace_bytes(R, N, K)), "wgrad")
+            _lib.launch("dg_skinny_linear_wgrad", x2, _lib.ptr(dy2), _lib.ptr(x2), _lib.ptr(dw), _lib.ptr(db), ws.data_ptr(),
+                        ws.numel(), R, N, K, _lib.dt(x2))
+            _account("linear_wgrad", x2.element_size() * R * K + 4 * R * N)
         return (None if dx is None else dx.view(x.shape)), dw, db
 
 
@@ -84,11 +71,8 @@ class _NodeEmbed(Function):
         R = z2.shape[0]
         a1 = torch.empty(R, 64, dtype=torch.float32, device=z.device)
         a2 = torch.empty(R, 128, dtype=torch.float32, device=z.device)
-        lib = _lib.load()
-        with _dev(z2):
-            _lib.check(lib.dg_embed_node_chain(_lib.ptr(z2), None, None, _lib.fptr(_c(w1)), _lib.fptr(_c(b1)), _lib.fptr(_c(w2)),
-                                               _lib.fptr(_c(b2)), _lib.ptr(a1), _lib.ptr(a2), R, E, act, _lib.stream_of(z2)),
-                       "dg_embed_node_chain")
+        _lib.launch("dg_embed_node_chain", z2, _lib.ptr(z2), None, None, _lib.fptr(_c(w1)), _lib.fptr(_c(b1)),
+                    _lib.fptr(_c(w2)), _lib.fptr(_c(b2)), _lib.ptr(a1), _lib.ptr(a2), R, E, act)
         ctx.save_for_backward(z2, a1, a2, w1, w2)
         ctx.act, ctx.zshape = act, z.shape
         return a2.view(*z.shape[:-1], 128)
@@ -111,11 +95,8 @@ class _NodeEmbedBwd(Function):
         g2 = torch.empty(R, 128, dtype=torch.float32, device=dev)
         g1 = torch.empty(R, 64, dtype=torch.float32, device=dev)
         dz = torch.empty(R, E, dtype=torch.float32, device=dev) if need_z else None
-        lib = _lib.load()
-        with _dev(z2):
-            _lib.check(lib.dg_embed_node_bwd(_lib.ptr(g), _lib.ptr(a1), _lib.ptr(a2), _lib.fptr(_c(w1)), _lib.fptr(_c(w2)),
-                                             _lib.ptr(g2), _lib.ptr(g1), _lib.ptr(dz), R, E, act, _lib.stream_of(z2)),
-                       "dg_embed_node_bwd")
+        _lib.launch("dg_embed_node_bwd", z2, _lib.ptr(g), _lib.ptr(a1), _lib.ptr(a2), _lib.fptr(_c(w1)), _lib.fptr(_c(w2)),
+                    _lib.ptr(g2), _lib.ptr(g1), _lib.ptr(dz), R, E, act)
         dw1 = db1 = dw2 = db2 = None
         if need_w:
             dw2, db2 = _wgrad(g2, a1, True)
@@ -138,11 +119,8 @@ class _NodeEmbedBwd(Function):
         dev = z2.device
         u1 = torch.empty(R, 64, dtype=torch.float32, device=dev)
         u2 = torch.empty(R, 128, dtype=torch.float32, device=dev)
-        lib = _lib.load()
-        with _dev(z2):
-            _lib.check(lib.dg_embed_node_chain(_lib.ptr(t), _lib.ptr(a1), _lib.ptr(a2), _lib.fptr(_c(w1)), None, _lib.fptr(_c(w2)),
-                                               None, _lib.ptr(u1), _lib.ptr(u2), R, E, ctx.act, _lib.stream_of(z2)),
-                       "dg_embed_node_chain")
+        _lib.launch("dg_embed_node_chain", z2, _lib.ptr(t), _lib.ptr(a1), _lib.ptr(a2), _lib.fptr(_c(w1)), None,
+                    _lib.fptr(_c(w2)), None, _lib.ptr(u1), _lib.ptr(u2), R, E, ctx.act)
         gw1 = gw2 = None
         if not _inputs_only():
             gw1, _ = _wgrad(g1, t, False)
@@ -162,10 +140,6 @@ def node_embed(z, l1, l2, act_name):
     return _NodeEmbed.apply(z, l1.weight, l1.bias, l2.weight, l2.bias, _HEAD_ACTS[act_name])
 
 
-def _head_launch(fn, name, *args):
-    _lib.check(fn(*args), name)
-
-
 class _HeadTail(Function):
     """Tail of the Discriminator head after its first Linear (reference models.py:173-178, 207): act - Linear(64, 32) - act -
     Linear(32, 16) - act - Linear(16, 1) over the rows of ``z1`` as ONE launch (dg_head_chain); the backward is one launch
@@ -179,11 +153,9 @@ class _HeadTail(Function):
         dev = z1.device
         a1, a2, a3 = (torch.empty(R, n, dtype=torch.float32, device=dev) for n in (64, 32, 16))
         out = torch.empty(R, 1, dtype=torch.float32, device=dev)
-        lib = _lib.load()
-        with _dev(z1):
-            _head_launch(lib.dg_head_chain, "dg_head_chain", _lib.ptr(z1), None, None, None, _lib.fptr(_c(w2)), _lib.fptr(_c(b2)),
-                         _lib.fptr(_c(w3)), _lib.fptr(_c(b3)), _lib.fptr(_c(w4)), _lib.fptr(_c(b4)), _lib.ptr(a1), _lib.ptr(a2),
-                         _lib.ptr(a3), _lib.ptr(out), R, act, _lib.stream_of(z1))
+        _lib.launch("dg_head_chain", z1, _lib.ptr(z1), None, None, None, _lib.fptr(_c(w2)), _lib.fptr(_c(b2)),
+                    _lib.fptr(_c(w3)), _lib.fptr(_c(b3)), _lib.fptr(_c(w4)), _lib.fptr(_c(b4)), _lib.ptr(a1), _lib.ptr(a2),
+                    _lib.ptr(a3), _lib.ptr(out), R, act)
         ctx.save_for_backward(a1, a2, a3, w2, w3, w4)
         ctx.act = act
         return out
@@ -203,19 +175,16 @@ class _HeadTailBwd(Function):
         R = a1.shape[0]
         dev = a1.device
         g3, g2, g1 = (torch.empty(R, n, dtype=torch.float32, device=dev) for n in (16, 32, 64))
-        lib = _lib.load()
         dws = [None] * 6
-        with _dev(a1):
-            st = _lib.stream_of(a1)
-            _head_launch(lib.dg_head_bwd, "dg_head_bwd", _lib.ptr(g_out), _lib.ptr(a1), _lib.ptr(a2), _lib.ptr(a3), _lib.fptr(_c(w2)),
-                         _lib.fptr(_c(w3)), _lib.fptr(_c(w4)), _lib.ptr(g3), _lib.ptr(g2), _lib.ptr(g1), R, act, st)
-            if need_w:
-                dw2, dw3, dw4 = torch.empty_like(w2), torch.empty_like(w3), torch.empty_like(w4)
-                db2, db3, db4 = (torch.empty(n, dtype=torch.float32, device=dev) for n in (32, 16, 1))
-                _head_launch(lib.dg_head_wgrad, "dg_head_wgrad", _lib.ptr(g_out), _lib.ptr(a3), _lib.ptr(g3), _lib.ptr(a2), _lib.ptr(g2),
-                             _lib.ptr(a1), _lib.ptr(dw4), _lib.ptr(db4), _lib.ptr(dw3), _lib.ptr(db3), _lib.ptr(dw2), _lib.ptr(db2),
-                             R, st)
-                dws = [dw2, db2, dw3, db3, dw4, db4]
+        _lib.launch("dg_head_bwd", a1, _lib.ptr(g_out), _lib.ptr(a1), _lib.ptr(a2), _lib.ptr(a3), _lib.fptr(_c(w2)),
+                    _lib.fptr(_c(w3)), _lib.fptr(_c(w4)), _lib.ptr(g3), _lib.ptr(g2), _lib.ptr(g1), R, act)
+        if need_w:
+            dw2, dw3, dw4 = torch.empty_like(w2), torch.empty_like(w3), torch.empty_like(w4)
+            db2, db3, db4 = (torch.empty(n, dtype=torch.float32, device=dev) for n in (32, 16, 1))
+            _lib.launch("dg_head_wgrad", a1, _lib.ptr(g_out), _lib.ptr(a3), _lib.ptr(g3), _lib.ptr(a2), _lib.ptr(g2),
+                        _lib.ptr(a1), _lib.ptr(dw4), _lib.ptr(db4), _lib.ptr(dw3), _lib.ptr(db3), _lib.ptr(dw2),
+                        _lib.ptr(db2), R)
+            dws = [dw2, db2, dw3, db3, dw4, db4]
         ctx.save_for_backward(g_out, a1, a2, a3, w2, w3, w4, g2, g3)
         ctx.act = act
         ctx.set_materialize_grads(False)
@@ -234,17 +203,14 @@ class _HeadTailBwd(Function):
         dev = a1.device
         u1, u2, u3 = (torch.empty(R, n, dtype=torch.float32, device=dev) for n in (64, 32, 16))
         uo = torch.empty(R, 1, dtype=torch.float32, device=dev)
-        lib = _lib.load()
         gw2 = gw3 = gw4 = None
-        with _dev(a1):
-            st = _lib.stream_of(a1)
-            _head_launch(lib.dg_head_chain, "dg_head_chain", _lib.ptr(t1), _lib.ptr(a1), _lib.ptr(a2), _lib.ptr(a3), _lib.fptr(_c(w2)),
-                         None, _lib.fptr(_c(w3)), None, _lib.fptr(_c(w4)), None, _lib.ptr(u1), _lib.ptr(u2), _lib.ptr(u3),
-                         _lib.ptr(uo), R, ctx.act, st)
-            if not _inputs_only():
-                gw2, gw3, gw4 = torch.empty_like(w2), torch.empty_like(w3), torch.empty_like(w4)
-                _head_launch(lib.dg_head_wgrad, "dg_head_wgrad", _lib.ptr(g_out), _lib.ptr(u3), _lib.ptr(g3), _lib.ptr(u2), _lib.ptr(g2),
-                             _lib.ptr(u1), _lib.ptr(gw4), None, _lib.ptr(gw3), None, _lib.ptr(gw2), None, R, st)
+        _lib.launch("dg_head_chain", a1, _lib.ptr(t1), _lib.ptr(a1), _lib.ptr(a2), _lib.ptr(a3), _lib.fptr(_c(w2)), None,
+                    _lib.fptr(_c(w3)), None, _lib.fptr(_c(w4)), None, _lib.ptr(u1), _lib.ptr(u2), _lib.ptr(u3), _lib.ptr(uo),
+                    R, ctx.act)
+        if not _inputs_only():
+            gw2, gw3, gw4 = torch.empty_like(w2), torch.empty_like(w3), torch.empty_like(w4)
+            _lib.launch("dg_head_wgrad", a1, _lib.ptr(g_out), _lib.ptr(u3), _lib.ptr(g3), _lib.ptr(u2), _lib.ptr(g2),
+                        _lib.ptr(u1), _lib.ptr(gw4), None, _lib.ptr(gw3), None, _lib.ptr(gw2), None, R)
         # act'' = 0: nothing reaches the forward's activations
         return uo, None, None, None, gw2, gw3, gw4, None, None
 
@@ -269,6 +235,3 @@ def readout(x, weight, bias=None):
     if not ok:
         return linear(x.float(), weight, bias)
     return _Readout.apply(x, weight, bias)
-
-
-__all__ = [_n for _n in dir() if not _n.startswith("__")]

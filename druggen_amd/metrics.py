@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .functional import _c, _dev
+from .functional import _c
 
 __all__ = ["PackedFingerprints", "pack_bits_numpy", "pack_fingerprints", "tanimoto_aggregate", "average_agg_tanimoto",
            "internal_diversity"]
@@ -84,9 +84,7 @@ def pack_fingerprints(x, device=None):
         words = torch.empty((n, nbits // 32), dtype=torch.int32, device=x.device)
         counts = torch.empty((n,), dtype=torch.int32, device=x.device)
         if n:
-            with _dev(x):
-                _lib.check(_lib.load().dg_fp_pack(x.data_ptr(), _DENSE[x.dtype], n, nbits, words.data_ptr(),
-                                                  counts.data_ptr(), _lib.stream_of(x)), "dg_fp_pack")
+            _lib.launch("dg_fp_pack", x, x.data_ptr(), _DENSE[x.dtype], n, nbits, words.data_ptr(), counts.data_ptr())
         return PackedFingerprints(words, counts, nbits)
     words, counts = pack_bits_numpy(x)
     device = _cuda_device(device)
@@ -136,10 +134,9 @@ def tanimoto_aggregate(stock, gen, agg="max", return_index=False):
     work = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
     out = torch.empty((G,), dtype=torch.float64 if mean else torch.float32, device=dev)
     idx = torch.empty((G,), dtype=torch.int32, device=dev) if return_index else None
-    with _dev(gw):
-        _lib.check(lib.dg_fp_tanimoto(sw.data_ptr(), sc.data_ptr(), S, gw.data_ptr(), gc.data_ptr(), G, gen.nbits,
-                                      _MODES[agg], out.data_ptr(), None if idx is None else idx.data_ptr(),
-                                      None if work is None else work.data_ptr(), need, _lib.stream_of(gw)), "dg_fp_tanimoto")
+    _lib.launch("dg_fp_tanimoto", gw, sw.data_ptr(), sc.data_ptr(), S, gw.data_ptr(), gc.data_ptr(), G, gen.nbits,
+                _MODES[agg], out.data_ptr(), None if idx is None else idx.data_ptr(),
+                None if work is None else work.data_ptr(), need)
     out = out if mean else out.double()      # float32 -> float64 is exact
     return (out, idx) if return_index else out
 

@@ -15,7 +15,7 @@ from typing import Iterable, List, Optional
 import torch
 
 from . import _lib
-from .functional import _dev, repack_params
+from .functional import repack_params
 
 __all__ = ["FlatAdamW"]
 
@@ -86,16 +86,12 @@ class FlatAdamW:
         if self.flat_grad is None:
             return
         self.step_count += 1
-        lib = _lib.load()
         if self.device_step is None:
             self.device_step = torch.full((1,), self.step_count - 1, dtype=torch.int32, device=self.flat_param.device)
-        with _dev(self.flat_param):
-            # step count in device memory: the launch stays correct when captured into a hipGraph
-            _lib.check(lib.dg_adamw_flat_devstep(self.flat_param.data_ptr(), self.flat_grad.data_ptr(),
-                                                 self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                                                 self.flat_param.numel(), self.lr, self.betas[0], self.betas[1],
-                                                 self.eps, self.weight_decay, self.device_step.data_ptr(),
-                                                 _lib.stream_of(self.flat_param)), "dg_adamw_flat_devstep")
+        # step count in device memory: the launch stays correct when captured into a hipGraph
+        _lib.launch("dg_adamw_flat_devstep", self.flat_param, self.flat_param.data_ptr(), self.flat_grad.data_ptr(),
+                    self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.flat_param.numel(), self.lr, self.betas[0],
+                    self.betas[1], self.eps, self.weight_decay, self.device_step.data_ptr())
         # the kernel wrote the parameters behind autograd's back: bump their version counters so that
         # version-keyed caches (packed GEMM weights) notice, exactly as an in-place torch op would
         # (only THESE parameters go stale: a global epoch bump here made every step re-pack the other network's

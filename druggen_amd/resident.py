@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .functional import _dev, attach_one_hot_labels
+from .functional import attach_one_hot_labels
 
 __all__ = ["ResidentMolecules", "epoch_batches", "MAX_VERTEXES", "MAX_B_DIM", "MAX_M_DIM"]
 
@@ -230,10 +230,8 @@ class ResidentMolecules:
             if not capturing:
                 self.raise_bad_indices()      # counters of earlier calls whose host copies are complete by now
             bad = self._captured_bad if capturing else torch.empty(1, dtype=torch.int32, device=self.device)
-            with _dev(a):
-                _lib.check(_lib.load().dg_mol_gather(self.atoms.data_ptr(), self.ptr.data_ptr(), self.entries.data_ptr(), self.n,
-                                                     index.data_ptr(), B, N, M, E, a.data_ptr(), labels.data_ptr(),
-                                                     x.data_ptr(), bad.data_ptr(), _lib.stream_of(a)), "dg_mol_gather")
+            _lib.launch("dg_mol_gather", a, self.atoms.data_ptr(), self.ptr.data_ptr(), self.entries.data_ptr(), self.n,
+                        index.data_ptr(), B, N, M, E, a.data_ptr(), labels.data_ptr(), x.data_ptr(), bad.data_ptr())
             if capturing:
                 self._captured = True
             else:

@@ -341,3 +341,20 @@ def test_onehot_embedding_matches_the_dense_kernel(B, N, E, act, dtype):
     assert torch.equal(dgf.one_hot_labels(dgf.as_one_hot(a)).cpu(), torch.from_numpy(bonds2).to(torch.int32))
     a.copy_(soft)
     assert dgf.one_hot_labels(dgf.as_one_hot(a)) is None
+
+
+def test_launch_reports_the_entry_and_keeps_the_current_device():
+    """``_lib.launch``: the entry's status comes back as ``check``'s RuntimeError under the entry's name (the entry returns from
+    its argument check: nothing is launched), and a ``ref`` on another device leaves the caller's device current."""
+    import re
+    from druggen_amd import _lib
+    args = (None, None, None, None, None, None, 1, 9, 128, 0.25, 0)
+    refs = [torch.zeros(4, device="cuda:0")]
+    if torch.cuda.device_count() >= 2:
+        refs.append(torch.zeros(4, device="cuda:1"))
+    torch.cuda.set_device(0)
+    for ref in refs:
+        with pytest.raises(RuntimeError, match=r"dg_attn_core_fwd failed \(-2\)") as err:
+            _lib.launch("dg_attn_core_fwd", ref, *args)
+        assert re.search("null pointer", str(err.value))
+        assert torch.cuda.current_device() == 0

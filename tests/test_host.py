@@ -32,6 +32,54 @@ def test_library_exports_every_declared_symbol():
     assert lib.dg_last_error_string() is not None
 
 
+def _ctypes_kind(ctype):
+    """The kind a ctypes parameter or return type has in the header's terms."""
+    import ctypes
+    from druggen_amd import _lib
+    named = {ctypes.c_int: "int", ctypes.c_int64: "int64_t", ctypes.c_size_t: "size_t", ctypes.c_float: "float",
+             ctypes.c_double: "double", ctypes.c_char_p: "pointer", ctypes.c_void_p: "pointer",
+             ctypes.POINTER(_lib.FFNFwdArgs): "dg_ffn_fwd_args*", ctypes.POINTER(_lib.FFNBwdArgs): "dg_ffn_bwd_args*"}
+    if ctype in named:
+        return named[ctype]
+    assert hasattr(ctype, "_type_") and ctype.__name__.startswith("LP_"), ctype      # a typed out-pointer (dg_prof_read)
+    return "pointer"
+
+
+def _header_kind(decl):
+    """Kind of one header parameter (or return type): ``decl`` is the declaration without its comments."""
+    decl = re.sub(r"\bconst\b", " ", decl).strip()
+    for struct in ("dg_ffn_fwd_args", "dg_ffn_bwd_args"):
+        if re.match(rf"{struct}\s*\*", decl):
+            return struct + "*"
+    if "*" in decl or re.match(r"dg_stream_t\b", decl):
+        return "pointer"
+    kind = decl.split()[0]
+    assert kind in ("int", "int64_t", "size_t", "float", "double"), decl
+    return kind
+
+
+def test_ctypes_table_matches_header_parameter_by_parameter():
+    """Every prototype of the header against ``_lib.SIGNATURES``: return type, parameter count and each parameter's kind in
+    order -- a row that is one ``int64_t`` off would pass the name check above and corrupt memory on the GPU."""
+    from druggen_amd import _lib
+    header = open(os.path.join(ROOT, "include", "druggen_hip.h")).read()
+    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    header = re.sub(r"//[^\n]*", " ", header)
+    header = re.sub(r"^\s*#.*$", " ", header, flags=re.M)
+    protos = re.findall(r"([A-Za-z_][\w\s\*]*?)\b(dg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", header)
+    assert len(protos) == 93, len(protos)
+    assert {name for _, name, _ in protos} == set(_lib.SIGNATURES)
+    wrong = []
+    for ret, name, params in protos:
+        res, args = _lib.SIGNATURES[name]
+        params = [] if params.strip() in ("", "void") else [p for p in params.split(",")]
+        want = [_header_kind(ret)] + [_header_kind(p) for p in params]
+        got = [_ctypes_kind(res)] + [_ctypes_kind(a) for a in args]
+        if want != got:
+            wrong.append((name, want, got))
+    assert not wrong, wrong
+
+
 def test_argument_validation_needs_no_gpu():
     from druggen_amd import _lib
     lib = _lib.load()
