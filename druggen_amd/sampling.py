@@ -39,6 +39,7 @@ class MoleculeSampler:
         self._order2 = _order2_table(bond_order2, edge.shape[-1], node.device)      # on the device before any capture
         self.graph = None
         self._labels = None
+        self._shape = (tuple(edge.shape), tuple(node.shape))
         if not graph:
             return
         self._act_dtype = activation_dtype()
@@ -92,9 +93,7 @@ class MoleculeSampler:
             if tuple(edge.shape) != tuple(self.static_edge.shape) or tuple(node.shape) != tuple(self.static_node.shape):
                 raise RuntimeError(f"MoleculeSampler was captured for edge {tuple(self.static_edge.shape)} / node "
                                    f"{tuple(self.static_node.shape)}: build a new sampler for another batch shape")
-            if activation_dtype() != self._act_dtype:
-                raise RuntimeError(f"MoleculeSampler was captured with {self._act_dtype} activations: build a new sampler "
-                                   f"after set_activation_dtype")
+            self._check_activation_dtype()
             # validate BEFORE touching a static buffer: a rejected batch leaves the dense buffer and its labels consistent
             lab = None
             new_edge = edge.data_ptr() != self.static_edge.data_ptr()
@@ -112,8 +111,50 @@ class MoleculeSampler:
                     attach_one_hot_labels(self.static_edge, self._labels)
             if node.data_ptr() != self.static_node.data_ptr():
                 self.static_node.copy_(node)
-            if [p.data_ptr() for p in self.G.parameters()] != self._param_ptrs:
-                self._capture()      # parameters were moved (not just overwritten) since the capture
-            self.graph.replay()
-            out = self._static_out
+            out = self.replay()
+        return out if keep_logits else out[0]
+
+    def _check_activation_dtype(self):
+        if activation_dtype() != self._act_dtype:
+            raise RuntimeError(f"MoleculeSampler was captured with {self._act_dtype} activations: build a new sampler "
+                               f"after set_activation_dtype")
+
+    def inputs(self):
+        """``(a, labels, x)``: the static dense buffers and the static int32 label buffer the captured kernels read -- an
+        ``out=`` of ``ResidentMolecules.batch``.  Whoever writes ``a`` writes ``labels`` too, then calls ``replay``."""
+        if self.graph is None:
+            raise RuntimeError("MoleculeSampler(graph=False) has no static inputs")
+        if self._labels is None:
+            raise RuntimeError("MoleculeSampler was captured with an edge batch that is not one-hot: it has no label buffer "
+                               "(the graph embeds the dense tensor); refresh it through sample()")
+        return self.static_edge, self._labels, self.static_node
+
+    def replay(self):
+        """Forward and decode of whatever the static inputs hold now: ``(batch, node_sample, edge_sample)`` in static buffers."""
+        if self.graph is None:
+            raise RuntimeError("MoleculeSampler(graph=False) has nothing to replay")
+        if [p.data_ptr() for p in self.G.parameters()] != self._param_ptrs:
+            self._capture()      # parameters were moved (not just overwritten) since the capture
+        self.graph.replay()
+        return self._static_out
+
+    def sample_from(self, store, index, *, keep_logits: bool = False):
+        """``sample`` on the molecules ``index`` (int64 ``[B]``) of a ``resident.ResidentMolecules``.  Graphed: ``dg_mol_gather``
+        writes straight into the static inputs -- dense buffers and labels together -- and the graph is replayed; eager:
+        ``sample`` on the gathered batch, whose one-hot labels the store guarantees.  ``ValueError`` before any launch when the
+        store's ``(N, b_dim, m_dim)`` differ from the sampler's batch or, graphed, the index length from its ``B``."""
+        B = int(index.shape[0]) if torch.is_tensor(index) else len(index)
+        edge_shape, node_shape = self._shape
+        N, E, M = store.vertexes, store.b_dim, store.m_dim
+        if (N, N, E) != edge_shape[1:] or (N, M) != node_shape[1:]:
+            raise ValueError(f"sample_from: the store holds N={N}, b_dim={E}, m_dim={M}; the sampler was built for edge "
+                             f"{edge_shape} / node {node_shape}")
+        if self.graph is None:
+            _, a, x = store.batch(index)
+            return self.sample(a, x, keep_logits=keep_logits, check_one_hot=False)
+        if B != edge_shape[0]:
+            raise ValueError(f"sample_from: {B} indices, the sampler was captured for batches of {edge_shape[0]}")
+        self._check_activation_dtype()
+        store.batch(index, out=self.inputs())
+        out = self.replay()
         return out if keep_logits else out[0]

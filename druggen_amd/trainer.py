@@ -450,6 +450,19 @@ class GraphedGANStep:
             if lab is not None:
                 self._labels[idx].copy_(lab)      # in place: the captured kernels read this buffer
                 attach_one_hot_labels(dst, self._labels[idx])
+        return self.replay()
+
+    def inputs(self):
+        """``((disc_a, disc_labels, disc_x), (gen_a, gen_labels, gen_x))``: the static dense buffers and the static int32 label
+        buffers the captured kernels read -- each triple is an ``out=`` of ``ResidentMolecules.batch``.  Whoever writes a
+        dense buffer writes its labels too (and re-attaches them, as ``batch(out=...)`` does), then calls ``replay``."""
+        if 0 not in self._labels or 2 not in self._labels:
+            raise RuntimeError("GraphedGANStep was captured with an edge batch that is not one-hot: it has no label buffer "
+                               "(the graph embeds the dense tensors); refresh it through step()")
+        return ((self.static[0], self._labels[0], self.static[1]), (self.static[2], self._labels[2], self.static[3]))
+
+    def replay(self):
+        """One iteration on whatever the static inputs hold now; returns the static loss scalars."""
         if self.segments is None:
             self.graph.replay()
         else:
