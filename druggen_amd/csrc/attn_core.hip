@@ -23,39 +23,17 @@
 //     atomics and are bit-reproducible.  Row groups of one block are combined
 //     once at the end through LDS in a fixed order.
 //   * narrow models (C < 32) use fewer quads per slice (LQS) and more phases.
-#include "bf16.h"
+//
+// attn_core.h holds what this file shares with attn_core_long.hip (N <= 256, one workgroup per row): the lane layout,
+// the XCD-aware placement, the gate and the score, the second order's tangent and slot body, and the host side's
+// argument checks and instance dispatch.
+#include "attn_core.h"
 #include "traversal.h"
 
 #include <type_traits>
 
 namespace dg {
 namespace {
-
-constexpr float kNegBig = -3.0e38f;
-
-template <int LQS, int JPL>
-struct Lane {
-    static constexpr int QS = 1 << LQS;   // quads per slice
-    static constexpr int P = 64 >> LQS;   // neighbour phases per wave
-    int quad, phase;
-    bool cok;          // this lane's channels exist
-    int c0;            // channel offset (clamped to 0 when !cok)
-    unsigned off[JPL]; // element offset of (neighbour slot, channel) inside one [N,C] row block
-    bool jok[JPL];     // slot holds a real neighbour
-    __device__ __forceinline__ Lane(int lane, int slice, int N, int C) {
-        quad = lane & (QS - 1);
-        phase = lane >> LQS;
-        const int cq = slice * QS + quad;
-        cok = cq * 4 < C;
-        c0 = cok ? cq * 4 : 0;
-#pragma unroll
-        for (int t = 0; t < JPL; ++t) {
-            const int j = phase + t * P;
-            jok[t] = j < N;
-            off[t] = static_cast<unsigned>((jok[t] ? j : 0) * C + c0);   // clamped: loads stay in bounds, results are masked
-        }
-    }
-};
 
 // ---------------------------------------------------------------- forward ----
 template <typename T, int LQS, int JPL>
@@ -67,17 +45,10 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ q, 
     const int lane = threadIdx.x & 63;
     const int slice = blockIdx.y * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (slice * QS * 4 >= C) return;  // wave-uniform; no barriers in this kernel
-    // XCD-aware placement (speed only): workgroup id -> XCD is round robin (id % 8), and each XCD has its own L2.
-    // All RG row groups of a molecule get ids with the same residue mod 8, consecutive in that XCD's dispatch order,
-    // so the molecule's k, v rows are fetched from HBM once instead of once per XCD (PMC: reads 1.30x -> ~1.0x
-    // of the algorithmic bytes).
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    // (reverse, traversal.h: molecules in descending order -- b -> 8 ceil(B / 8) - 1 - b keeps a molecule's workgroups on one XCD)
-    int b = (slot / RG) * 8 + xcd;
-    const int rg = slot % RG;
-    if (reverse) b = (B + 7) / 8 * 8 - 1 - b;
+    int b, one_slice, rg;      // the RG row groups of a molecule share an XCD; the slice comes from blockIdx.y above
+    place(1, RG, B, reverse, b, one_slice, rg);
     if (b >= B) return;
-    const Lane<LQS, JPL> L(lane, slice, N, C);
+    const Lane<64, LQS, JPL> L(lane, slice, N, C);
     const size_t NC = static_cast<size_t>(N) * C;
 
     float4 kk[JPL], vv[JPL];
@@ -86,30 +57,28 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ q, 
         kk[t] = ld4(k + b * NC + L.off[t]);
         vv[t] = ld4(v + b * NC + L.off[t]);
     }
-    constexpr bool PF = false;   // a one-row-ahead prefetch measured slower here (4 waves per SIMD already overlap rows)
     typedef typename raw4<T>::type Raw;
     Raw re[JPL], rq;
+    // (a lambda like the backward's; a one-row-ahead prefetch measured slower here: 4 waves per SIMD already overlap rows)
     auto request = [&](int i) {
         const size_t row = static_cast<size_t>(b) * N + i;
         rq = ld_raw(q + row * C + L.c0);
 #pragma unroll
         for (int t = 0; t < JPL; ++t) re[t] = ld_raw_stream(e + row * NC + L.off[t]);
     };
-    if (PF && rg < N) request(rg);
     for (int i = rg; i < N; i += RG) {
         const size_t row = static_cast<size_t>(b) * N + i;
-        if (!PF) request(i);
+        request(i);
         const float4 aq = alpha * cvt_raw(rq);
         T* sr = s + row * NC;
         float4 sv[JPL];
 #pragma unroll
         for (int t = 0; t < JPL; ++t) sv[t] = cvt_raw(re[t]);
-        if (PF && i + RG < N) request(i + RG);
         float4 m = f4(kNegBig);
 #pragma unroll
         for (int t = 0; t < JPL; ++t) {
             const float4 ee = sv[t];
-            sv[t] = aq * kk[t] * fma4(ee, ee, ee);
+            sv[t] = score(aq, kk[t], ee);
             if (L.jok[t]) {
                 m = max4(m, sv[t]);
                 if (L.cok && s) st4_stream(sr + L.off[t], sv[t]);
@@ -151,15 +120,13 @@ __global__ __launch_bounds__(RW * 64, (JPL <= 6 ? 2 : 1)) void attn_bwd_kernel(
     // spilled after its load and reloaded at its store (279 us against 199 us for the plain kernel at configs[1]).
     constexpr bool STASH = ADDE && std::is_same<T, float>::value;
     float4* stash = red + (RW - 1) * 2 * JPL * 64 + rw * JPL * 64;      // [RW][JPL][64] behind the reduction area
-    // XCD-aware placement (speed only; workgroup id -> XCD is id % 8): the SL channel slices of a molecule get
-    // consecutive ids on ONE XCD, so they run at the same time behind the same L2.  With bf16 rows a slice covers
-    // 64 of the 128 bytes of a cache line: the other half is then an L2 hit instead of a second HBM fetch.
+    // place(SL, 1, ...) of attn_core.h written out: the call reorders the bf16 single-slot instances' registers
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     int b = (slot / SL) * 8 + xcd;
     const int slice = slot % SL;
     if (reverse) b = (B + 7) / 8 * 8 - 1 - b;      // molecules in descending order (traversal.h)
     if (b >= B) return;   // block-uniform
-    const Lane<LQS, JPL> L(lane, slice, N, C);
+    const Lane<64, LQS, JPL> L(lane, slice, N, C);
     const size_t NC = static_cast<size_t>(N) * C;
 
     if (rw == 0) {
@@ -178,7 +145,8 @@ __global__ __launch_bounds__(RW * 64, (JPL <= 6 ? 2 : 1)) void attn_bwd_kernel(
     // fp32 rows cost 4 registers per slot: no room for the second set, and that variant sits at the HBM roof already.
     constexpr bool PF = !std::is_same<T, float>::value;
     typedef typename raw4<T>::type Raw;
-    Raw re[JPL], rws[JPL], rae[(ADDE && !STASH) ? JPL : 1], rq, rwo;
+    constexpr bool RAE = ADDE && !STASH;      // add_e through registers
+    Raw re[JPL], rws[JPL], rae[RAE ? JPL : 1], rq, rwo;
     auto request = [&](int i) {
         const size_t row = static_cast<size_t>(b) * N + i;
         if (STASH) {      // first: every later wait for a register load of this row then covers them
@@ -193,7 +161,7 @@ __global__ __launch_bounds__(RW * 64, (JPL <= 6 ? 2 : 1)) void attn_bwd_kernel(
         for (int t = 0; t < JPL; ++t) {
             re[t] = ld_raw_stream(e + row * NC + L.off[t]);
             if (ws) rws[t] = ld_raw_stream(ws + row * NC + L.off[t]);
-            if (ADDE && !STASH) rae[(ADDE && !STASH) ? t : 0] = ld_raw_stream(add_e + row * NC + L.off[t]);
+            if (RAE) rae[RAE ? t : 0] = ld_raw_stream(add_e + row * NC + L.off[t]);
         }
     };
     if (PF && rw < N) request(rw);
@@ -206,18 +174,18 @@ __global__ __launch_bounds__(RW * 64, (JPL <= 6 ? 2 : 1)) void attn_bwd_kernel(
         const float4 woi = cvt_raw(rwo);
         T* der = de + row * NC;
         float4 ee[JPL], wss[JPL], pe[JPL];
-        Raw hae[(ADDE && !STASH) ? JPL : 1];      // still packed: converted at the store
+        Raw hae[RAE ? JPL : 1];      // still packed: converted at the store
 #pragma unroll
         for (int t = 0; t < JPL; ++t) {
             ee[t] = cvt_raw(re[t]);
             wss[t] = ws ? cvt_raw(rws[t]) : f4(0.f);
-            if (ADDE && !STASH) hae[(ADDE && !STASH) ? t : 0] = rae[(ADDE && !STASH) ? t : 0];
+            if (RAE) hae[RAE ? t : 0] = rae[RAE ? t : 0];
         }
         if (PF && i + RW < N) request(i + RW);
         float4 m = f4(kNegBig);
 #pragma unroll
         for (int t = 0; t < JPL; ++t) {
-            pe[t] = aq * kv[(0 * JPL + t) * 64 + kl] * fma4(ee[t], ee[t], ee[t]);
+            pe[t] = score(aq, kv[(0 * JPL + t) * 64 + kl], ee[t]);
             if (L.jok[t]) m = max4(m, pe[t]);
         }
         m = xor_max4<QS>(m);
@@ -241,14 +209,14 @@ __global__ __launch_bounds__(RW * 64, (JPL <= 6 ? 2 : 1)) void attn_bwd_kernel(
             float4 ds = fma4(p, woi * kv[(1 * JPL + t) * 64 + kl] - abar, wss[t]);
             if (!L.jok[t]) ds = f4(0.f);
             dvv[t] = fma4(p, woi, dvv[t]);
-            const float4 g = fma4(ee[t], ee[t], ee[t]);
+            const float4 g = gate(ee[t]);
             const float4 dsg = ds * g;
             dqa = fma4(dsg, kk, dqa);
             dkk[t] = fma4(dsg, aq, dkk[t]);
-            const float4 g1 = fma4(f4(2.f), ee[t], f4(1.f));
+            const float4 g1 = dgate(ee[t]);
             float4 dev = ds * aq * kk * g1;
             if (STASH) dev += stash[t * 64 + kl];
-            else if (ADDE) dev += cvt_raw(hae[(ADDE && !STASH) ? t : 0]);
+            else if (RAE) dev += cvt_raw(hae[RAE ? t : 0]);
             if (L.jok[t] && L.cok) st4_stream(der + L.off[t], dev);
             __builtin_amdgcn_sched_barrier(0);   // one slot at a time: bounds the live temporaries
         }
@@ -301,15 +269,13 @@ __global__ __launch_bounds__(RW * 64) void attn_bwd2_kernel(
     float4* red = kv + 4 * JPL * 64;  // [(RW-1)][2*JPL][64]
     const int lane = threadIdx.x & 63;
     const int rw = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // XCD-aware placement (speed only; workgroup id -> XCD is id % 8): the SL channel slices of a molecule get
-    // consecutive ids on ONE XCD, so they run at the same time behind the same L2.  With bf16 rows a slice covers
-    // 64 of the 128 bytes of a cache line: the other half is then an L2 hit instead of a second HBM fetch.
+    // place(SL, 1, ...) of attn_core.h written out: the call reorders the bf16 single-slot instances' registers
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     int b = (slot / SL) * 8 + xcd;
     const int slice = slot % SL;
     if (reverse) b = (B + 7) / 8 * 8 - 1 - b;      // molecules in descending order (traversal.h)
     if (b >= B) return;   // block-uniform
-    const Lane<LQS, JPL> L(lane, slice, N, C);
+    const Lane<64, LQS, JPL> L(lane, slice, N, C);
     const size_t NC = static_cast<size_t>(N) * C;
 
     if (rw == 0) {
@@ -364,8 +330,7 @@ __global__ __launch_bounds__(RW * 64) void attn_bwd2_kernel(
         float4 m = f4(kNegBig);
 #pragma unroll
         for (int t = 0; t < JPL; ++t) {
-            const float4 kk = kv[(0 * JPL + t) * 64 + kl];
-            pe[t] = aq * kk * fma4(ee[t], ee[t], ee[t]);
+            pe[t] = score(aq, kv[(0 * JPL + t) * 64 + kl], ee[t]);
             if (L.jok[t]) m = max4(m, pe[t]);
         }
         m = xor_max4<QS>(m);
@@ -388,10 +353,8 @@ __global__ __launch_bounds__(RW * 64) void attn_bwd2_kernel(
         for (int t = 0; t < JPL; ++t) {
             const float4 kk = kv[(0 * JPL + t) * 64 + kl];
             const float4 tkk = kv[(2 * JPL + t) * 64 + kl];
-            const float4 g = fma4(ee[t], ee[t], ee[t]);
-            const float4 g1 = fma4(f4(2.f), ee[t], f4(1.f));
             pe[t] = pe[t] * inv;  // p
-            sd[t] = alpha * (g * fma4(tqi, kk, qi * tkk) + qi * kk * g1 * tee[t]);
+            sd[t] = bwd2_tangent(alpha, ee[t], qi, kk, tqi, tkk, tee[t]);
             if (L.jok[t] && L.cok && gws) st4_stream(gwr + L.off[t], sd[t]);
             mm = fma4(pe[t], sd[t], mm);
         }
@@ -418,24 +381,8 @@ __global__ __launch_bounds__(RW * 64) void attn_bwd2_kernel(
             const float4 vv = kv[(1 * JPL + t) * 64 + kl];
             const float4 tkk = kv[(2 * JPL + t) * 64 + kl];
             const float4 tvv = kv[(3 * JPL + t) * 64 + kl];
-            const float4 p = pe[t];
-            const float4 a = woi * vv;
-            const float4 g = fma4(ee[t], ee[t], ee[t]);
-            const float4 g1 = fma4(f4(2.f), ee[t], f4(1.f));
-            float4 ds = fma4(p, a - abar, wss[t]);
-            if (!L.jok[t]) ds = f4(0.f);
-            const float4 pdot = p * (sd[t] - mm);
-            const float4 pbar = sd[t] * (a - abar) - mm * a + woi * tvv;
-            const float4 sbar = p * (pbar - PB);
-            const float4 g1te = g1 * tee[t];
-            // gq_i += sbar alpha k g + ds alpha (tk g + k g1 te)
-            gqa += sbar * kk * g + ds * fma4(tkk, g, kk * g1te);
-            // gk_j += sbar alpha q g + ds alpha (tq g + q g1 te)
-            gkk[t] += sbar * aq * g + alpha * (ds * fma4(tqi, g, qi * g1te));
-            gvv[t] = fma4(pdot, woi, gvv[t]);
-            // ge = sbar alpha q k g1 + ds alpha (tq k g1 + q tk g1 + 2 q k te)
-            const float4 gev = sbar * aq * kk * g1 +
-                               alpha * (ds * (g1 * fma4(tqi, kk, qi * tkk) + 2.f * (qi * kk * tee[t])));
+            const float4 gev = bwd2_slot(woi, vv, ee[t], pe[t], abar, wss[t], L.jok[t], sd[t], mm, tvv, PB, tee[t], kk, tkk,
+                                         aq, alpha, tqi, qi, gqa, gkk[t], gvv[t]);
             if (L.jok[t] && L.cok) st4_stream(ger + L.off[t], gev);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -469,10 +416,6 @@ __global__ __launch_bounds__(RW * 64) void attn_bwd2_kernel(
 }
 
 // ---------------------------------------------------------------- dispatch ----
-struct Geometry {
-    int lqs, jpl, slices;
-};
-
 // narrow = true (second-order kernel): for N > 48 a wave takes 16 channels x 16 neighbour phases instead of 32 x 8, so
 // a lane keeps 6 neighbour slots instead of 12 -- the 12-slot second-order kernel needs > 500 registers per lane and
 // spills 400 of them (N = 90: 1071 -> 433 us); the slices of a molecule share an XCD, so the half lines meet in L2.
@@ -498,11 +441,12 @@ bool pick_geometry(int N, int C, Geometry* g, bool narrow = false) {
     return false;
 }
 
-constexpr int kRW = 4;  // row groups (waves) per backward block
+// row groups (waves) per backward block; eight measured slower and are not instantiated
+constexpr int kRW = 4;
 
-#define DG_FOR_GEOMETRY(M)                                                          \
-    M(1, 1) M(1, 2) M(1, 3) M(2, 1) M(2, 2) M(2, 3) M(2, 6) M(3, 1) M(3, 2) M(3, 3) \
-        M(3, 6) M(3, 12)
+// the instantiated (LQS, JPL)
+using Geometries = Shapes<Shape<1, 1>, Shape<1, 2>, Shape<1, 3>, Shape<2, 1>, Shape<2, 2>, Shape<2, 3>, Shape<2, 6>,
+                          Shape<3, 1>, Shape<3, 2>, Shape<3, 3>, Shape<3, 6>, Shape<3, 12>>;
 
 }  // namespace
 }  // namespace dg
@@ -511,11 +455,10 @@ using namespace dg;
 
 extern "C" int dg_attn_core_fwd(const void* q_, const void* k_, const void* v_, const void* e_, void* s_, void* o_,
                                 int B, int N, int C, float alpha, int dtype, dg_stream_t stream_) {
-    if (!q_ || !k_ || !v_ || !e_ || !o_) return fail(DG_E_ARG, "dg_attn_core_fwd: null pointer");  // s may be NULL
-    if (!dtype_ok(dtype)) return fail(DG_E_ARG, "dg_attn_core_fwd: unknown dtype %d", dtype);
     Geometry g;
-    if (B < 0 || !pick_geometry(N, C, &g))
-        return fail(DG_E_SHAPE, "dg_attn_core_fwd: unsupported shape B=%d N=%d C=%d (need C%%4==0, C>=8, N<=96)", B, N, C);
+    const bool ok = B >= 0 && pick_geometry(N, C, &g);
+    if (int st = check_fwd("dg_attn_core_fwd", q_, k_, v_, e_, o_, dtype, {ok, B, N, C, " (need C%4==0, C>=8, N<=96)"}))
+        return st;
     if (B == 0) return 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const int wpb = g.slices < 4 ? g.slices : 4;
@@ -525,19 +468,14 @@ extern "C" int dg_attn_core_fwd(const void* q_, const void* k_, const void* v_, 
     dim3 grid(static_cast<unsigned>((B + 7) / 8 * 8) * RG, (g.slices + wpb - 1) / wpb), block(64 * wpb);
     ProfScope prof(DG_K_ATTN_FWD, stream);
     const int reverse = take_direction(static_cast<int64_t>(B) * N * N);      // per-molecule results: any order
-#define LAUNCH_T(T, LQS, JPL)                                                                                     \
-    hipLaunchKernelGGL((attn_fwd_kernel<T, LQS, JPL>), grid, block, 0, stream, static_cast<const T*>(q_),         \
-                       static_cast<const T*>(k_), static_cast<const T*>(v_), static_cast<const T*>(e_),          \
-                       static_cast<T*>(s_), static_cast<T*>(o_), N, C, alpha, RG, B, reverse);
-#define LAUNCH(LQS, JPL)                                       \
-    if (g.lqs == LQS && g.jpl == JPL) {                        \
-        if (dtype == DG_DTYPE_BF16) { LAUNCH_T(bf16_t, LQS, JPL) } \
-        else { LAUNCH_T(float, LQS, JPL) }                     \
-    }
-    DG_FOR_GEOMETRY(LAUNCH)
-#undef LAUNCH
-#undef LAUNCH_T
-    return check_launch("dg_attn_core_fwd");
+    return dispatch(Geometries(), "dg_attn_core_fwd", dtype, g.lqs, g.jpl, [&](auto t, auto sh) {
+        using T = decltype(t);
+        using S = decltype(sh);
+        hipLaunchKernelGGL((attn_fwd_kernel<T, S::LQS, S::JPL>), grid, block, 0, stream, static_cast<const T*>(q_),
+                           static_cast<const T*>(k_), static_cast<const T*>(v_), static_cast<const T*>(e_),
+                           static_cast<T*>(s_), static_cast<T*>(o_), N, C, alpha, RG, B, reverse);
+        return 0;
+    });
 }
 
 extern "C" int dg_attn_core_bwd(const void* q_, const void* k_, const void* v_, const void* e_, const void* ws_,
@@ -549,87 +487,59 @@ extern "C" int dg_attn_core_bwd(const void* q_, const void* k_, const void* v_, 
 extern "C" int dg_attn_core_bwd_add(const void* q_, const void* k_, const void* v_, const void* e_, const void* ws_,
                                     const void* wo_, const void* add_e_, void* dq_, void* dk_, void* dv_, void* de_, int B,
                                     int N, int C, float alpha, int dtype, dg_stream_t stream_) {
-    if (!q_ || !k_ || !v_ || !e_ || !wo_ || !dq_ || !dk_ || !dv_ || !de_)
-        return fail(DG_E_ARG, "dg_attn_core_bwd: null pointer");  // ws may be NULL (= zeros)
-    if (!dtype_ok(dtype)) return fail(DG_E_ARG, "dg_attn_core_bwd: unknown dtype %d", dtype);
     Geometry g;
-    if (B < 0 || !pick_geometry(N, C, &g))
-        return fail(DG_E_SHAPE, "dg_attn_core_bwd: unsupported shape B=%d N=%d C=%d", B, N, C);
+    const bool ok = B >= 0 && pick_geometry(N, C, &g);
+    if (int st = check_bwd("dg_attn_core_bwd", q_, k_, v_, e_, wo_, dq_, dk_, dv_, de_, dtype, {ok, B, N, C, ""}))
+        return st;
     if (B == 0) return 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const bool rw8 = false;      // (eight row-group waves per workgroup measured slower than kRW: not offered)
-    dim3 grid(static_cast<unsigned>((B + 7) / 8 * 8) * g.slices), block(64 * (rw8 ? 8 : kRW));
+    dim3 grid(static_cast<unsigned>((B + 7) / 8 * 8) * g.slices), block(64 * kRW);
     ProfScope prof(DG_K_ATTN_BWD, stream);
     const int reverse = take_direction(static_cast<int64_t>(B) * N * N);      // per-molecule results: any order
-#define LAUNCH_T(T, LQS, JPL, RW_)                                                                              \
-    {                                                                                                           \
-        constexpr int lds = (2 * JPL + (RW_ - 1) * 2 * JPL + RW_ * JPL) * 64 * 16;   /* + the add_e stash */    \
-        if (add_e_) {                                                                                           \
-            DG_OPT_IN_LDS((&attn_bwd_kernel<T, LQS, JPL, RW_, true>), lds);                                      \
-            hipLaunchKernelGGL((attn_bwd_kernel<T, LQS, JPL, RW_, true>), grid, block, lds, stream,              \
-                               static_cast<const T*>(q_), static_cast<const T*>(k_), static_cast<const T*>(v_), \
-                               static_cast<const T*>(e_), static_cast<const T*>(ws_), static_cast<const T*>(wo_), \
-                               static_cast<const T*>(add_e_), static_cast<T*>(dq_), static_cast<T*>(dk_),       \
-                               static_cast<T*>(dv_), static_cast<T*>(de_), N, C, alpha, g.slices, B, reverse);           \
-        } else {                                                                                                \
-            DG_OPT_IN_LDS((&attn_bwd_kernel<T, LQS, JPL, RW_>), lds);                                            \
-            hipLaunchKernelGGL((attn_bwd_kernel<T, LQS, JPL, RW_>), grid, block, lds, stream,                    \
-                               static_cast<const T*>(q_), static_cast<const T*>(k_), static_cast<const T*>(v_), \
-                               static_cast<const T*>(e_), static_cast<const T*>(ws_), static_cast<const T*>(wo_), \
-                               static_cast<const T*>(nullptr), static_cast<T*>(dq_), static_cast<T*>(dk_),      \
-                               static_cast<T*>(dv_), static_cast<T*>(de_), N, C, alpha, g.slices, B, reverse);           \
-        }                                                                                                       \
-    }
-#define LAUNCH_RW(LQS, JPL, RW_)                                        \
-    {                                                                   \
-        if (dtype == DG_DTYPE_BF16) LAUNCH_T(bf16_t, LQS, JPL, RW_)     \
-        else LAUNCH_T(float, LQS, JPL, RW_)                             \
-    }
-#define LAUNCH(LQS, JPL)                                  \
-    if (g.lqs == LQS && g.jpl == JPL) {                   \
-        if (rw8 && JPL <= 6) LAUNCH_RW(LQS, (JPL <= 6 ? JPL : 1), 8) else LAUNCH_RW(LQS, JPL, kRW) \
-    }
-    DG_FOR_GEOMETRY(LAUNCH)
-#undef LAUNCH
-#undef LAUNCH_RW
-#undef LAUNCH_T
-    return check_launch("dg_attn_core_bwd");
+    return dispatch(Geometries(), "dg_attn_core_bwd", dtype, g.lqs, g.jpl, [&](auto t, auto sh) {
+        using T = decltype(t);
+        constexpr int LQS = decltype(sh)::LQS, JPL = decltype(sh)::JPL;
+        constexpr int lds = (2 * JPL + (kRW - 1) * 2 * JPL + kRW * JPL) * 64 * 16;   // k, v + the reduction area + the add_e stash
+        auto launch = [&](auto adde) {
+            constexpr bool ADDE = decltype(adde)::value;
+            DG_OPT_IN_LDS((&attn_bwd_kernel<T, LQS, JPL, kRW, ADDE>), lds);
+            hipLaunchKernelGGL((attn_bwd_kernel<T, LQS, JPL, kRW, ADDE>), grid, block, lds, stream,
+                               static_cast<const T*>(q_), static_cast<const T*>(k_), static_cast<const T*>(v_),
+                               static_cast<const T*>(e_), static_cast<const T*>(ws_), static_cast<const T*>(wo_),
+                               static_cast<const T*>(add_e_), static_cast<T*>(dq_), static_cast<T*>(dk_),
+                               static_cast<T*>(dv_), static_cast<T*>(de_), N, C, alpha, g.slices, B, reverse);
+            return 0;
+        };
+        return add_e_ ? launch(std::true_type()) : launch(std::false_type());
+    });
 }
 
 extern "C" int dg_attn_core_bwd2(const void* q_, const void* k_, const void* v_, const void* e_, const void* ws_,
                                  const void* wo_, const void* tq_, const void* tk_, const void* tv_, const void* te_,
                                  void* gq_, void* gk_, void* gv_, void* ge_, void* gws_, void* gwo_, int B, int N,
                                  int C, float alpha, int dtype, dg_stream_t stream_) {
-    if (!q_ || !k_ || !v_ || !e_ || !wo_ || !tq_ || !tk_ || !tv_ || !te_ || !gq_ || !gk_ || !gv_ || !ge_ || !gwo_)  // ws, gws may be NULL
-        return fail(DG_E_ARG, "dg_attn_core_bwd2: null pointer");
-    if (!dtype_ok(dtype)) return fail(DG_E_ARG, "dg_attn_core_bwd2: unknown dtype %d", dtype);
     Geometry g;
-    if (B < 0 || !pick_geometry(N, C, &g, true))
-        return fail(DG_E_SHAPE, "dg_attn_core_bwd2: unsupported shape B=%d N=%d C=%d", B, N, C);
+    const bool ok = B >= 0 && pick_geometry(N, C, &g, true);
+    if (int st = check_bwd2("dg_attn_core_bwd2", q_, k_, v_, e_, wo_, tq_, tk_, tv_, te_, gq_, gk_, gv_, ge_, gwo_, dtype,
+                            {ok, B, N, C, ""}))
+        return st;
     if (B == 0) return 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     dim3 grid(static_cast<unsigned>((B + 7) / 8 * 8) * g.slices), block(64 * kRW);
     ProfScope prof(DG_K_ATTN_BWD2, stream);
     const int reverse = take_direction(static_cast<int64_t>(B) * N * N);      // per-molecule results: any order
-#define LAUNCH_T(T, LQS, JPL)                                                                                     \
-    {                                                                                                             \
-        constexpr int lds = (4 * JPL + (kRW - 1) * 2 * JPL) * 64 * 16;                                            \
-        DG_OPT_IN_LDS((&attn_bwd2_kernel<T, LQS, JPL, kRW>), lds);                                                 \
-        hipLaunchKernelGGL((attn_bwd2_kernel<T, LQS, JPL, kRW>), grid, block, lds, stream,                         \
-                           static_cast<const T*>(q_), static_cast<const T*>(k_), static_cast<const T*>(v_),       \
-                           static_cast<const T*>(e_), static_cast<const T*>(ws_), static_cast<const T*>(wo_),     \
-                           static_cast<const T*>(tq_), static_cast<const T*>(tk_), static_cast<const T*>(tv_),    \
-                           static_cast<const T*>(te_), static_cast<T*>(gq_), static_cast<T*>(gk_),                \
-                           static_cast<T*>(gv_), static_cast<T*>(ge_), static_cast<T*>(gws_), static_cast<T*>(gwo_), \
-                           N, C, alpha, g.slices, B, reverse);                                                             \
-    }
-#define LAUNCH(LQS, JPL)                                   \
-    if (g.lqs == LQS && g.jpl == JPL) {                    \
-        if (dtype == DG_DTYPE_BF16) LAUNCH_T(bf16_t, LQS, JPL) \
-        else LAUNCH_T(float, LQS, JPL)                     \
-    }
-    DG_FOR_GEOMETRY(LAUNCH)
-#undef LAUNCH
-#undef LAUNCH_T
-    return check_launch("dg_attn_core_bwd2");
+    return dispatch(Geometries(), "dg_attn_core_bwd2", dtype, g.lqs, g.jpl, [&](auto t, auto sh) {
+        using T = decltype(t);
+        constexpr int LQS = decltype(sh)::LQS, JPL = decltype(sh)::JPL;
+        constexpr int lds = (4 * JPL + (kRW - 1) * 2 * JPL) * 64 * 16;
+        DG_OPT_IN_LDS((&attn_bwd2_kernel<T, LQS, JPL, kRW>), lds);
+        hipLaunchKernelGGL((attn_bwd2_kernel<T, LQS, JPL, kRW>), grid, block, lds, stream,
+                           static_cast<const T*>(q_), static_cast<const T*>(k_), static_cast<const T*>(v_),
+                           static_cast<const T*>(e_), static_cast<const T*>(ws_), static_cast<const T*>(wo_),
+                           static_cast<const T*>(tq_), static_cast<const T*>(tk_), static_cast<const T*>(tv_),
+                           static_cast<const T*>(te_), static_cast<T*>(gq_), static_cast<T*>(gk_),
+                           static_cast<T*>(gv_), static_cast<T*>(ge_), static_cast<T*>(gws_), static_cast<T*>(gwo_),
+                           N, C, alpha, g.slices, B, reverse);
+        return 0;
+    });
 }

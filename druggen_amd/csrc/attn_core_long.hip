@@ -1,5 +1,7 @@
 // Graph attention core (reference src/model/layers.py:119-134) for long neighbour lists: 1 <= N <= 256.
-// Same math as csrc/attn_core.hip (forward, backward with the add_e adjoint, backward of backward):
+// Forward, backward with the add_e adjoint, backward of backward.  The lane layout, the XCD-aware placement, the gate and
+// the score, the second order's tangent, and the host side's argument checks and instance dispatch are csrc/attn_core.h,
+// shared with attn_core.hip:
 //
 //   s_ij = alpha q_i k_j (e_ij^2 + e_ij)     p_ij = softmax_j s_ij     o_i = sum_j p_ij v_j
 //
@@ -18,7 +20,7 @@
 //     rows of a molecule are split over G row groups (workgroups); each writes its column sums to a float32 workspace
 //     [2][G][B,N,C] and a second launch adds the G partials in ascending order.  No atomics: bit-reproducible in both
 //     traversal directions.
-#include "bf16.h"
+#include "attn_core.h"
 #include "traversal.h"
 
 #include <type_traits>
@@ -26,50 +28,9 @@
 namespace dg {
 namespace {
 
-constexpr float kNegBigL = -3.0e38f;
 constexpr int kThreads = 256;      // four waves per workgroup
 constexpr int kFwdRows = 16;       // rows per forward workgroup: the k, v staging is 2/16 of the row traffic
 constexpr int kBwdRows = 32;       // rows per backward workgroup: the column partials are 2/32 of a row tensor
-
-template <int LQS, int JPL>
-struct LongLane {
-    static constexpr int QS = 1 << LQS;          // quads per slice
-    static constexpr int P = kThreads >> LQS;    // neighbour phases per workgroup
-    int quad;
-    bool cok;              // this thread's channels exist
-    int c0;                // channel offset (0 when !cok)
-    unsigned off[JPL];     // element offset of (neighbour slot, channel) inside one [N,C] block
-    bool jok[JPL];         // slot holds a real neighbour
-    __device__ __forceinline__ LongLane(int tid, int slice, int N, int C) {
-        quad = tid & (QS - 1);
-        const int phase = tid >> LQS;
-        const int cq = slice * QS + quad;
-        cok = cq * 4 < C;
-        c0 = cok ? cq * 4 : 0;
-#pragma unroll
-        for (int t = 0; t < JPL; ++t) {
-            const int j = phase + t * P;
-            jok[t] = j < N;
-            off[t] = static_cast<unsigned>((jok[t] ? j : 0) * C + c0);   // clamped: loads stay in bounds, results are masked
-        }
-    }
-};
-
-// workgroup -> (molecule, channel slice, row group).  Workgroup id -> XCD is id % 8: every workgroup of a molecule gets
-// the same residue and consecutive ids, so its k, v rows are fetched once per XCD and the slices sharing a cache line
-// run together behind one L2.  reverse: molecules in descending order (traversal.h).
-struct Place {
-    int b, slice, group;
-};
-__device__ __forceinline__ Place place(int SL, int G, int B, int reverse) {
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per = SL * G;
-    Place p;
-    p.b = (slot / per) * 8 + xcd;
-    p.slice = (slot % per) % SL;
-    p.group = (slot % per) / SL;
-    if (reverse) p.b = (B + 7) / 8 * 8 - 1 - p.b;
-    return p;
-}
 
 // ---------------------------------------------------------------- forward ----
 template <typename T, int LQS, int JPL>
@@ -83,7 +44,7 @@ __global__ __launch_bounds__(kThreads, 2) void attn_long_fwd_kernel(const T* __r
     const Place pl = place(SL, G, B, reverse);
     if (pl.b >= B) return;   // workgroup-uniform
     const int b = pl.b;
-    const LongLane<LQS, JPL> L(tid, pl.slice, N, C);
+    const Lane<kThreads, LQS, JPL> L(tid, pl.slice, N, C);
     const size_t NC = static_cast<size_t>(N) * C;
     float4 kk[JPL], vv[JPL];
 #pragma unroll
@@ -102,11 +63,11 @@ __global__ __launch_bounds__(kThreads, 2) void attn_long_fwd_kernel(const T* __r
         const float4 aq = alpha * ld4(q + row * C + L.c0);
         T* sr = s + row * NC;
         float4 sv[JPL];
-        float4 m = f4(kNegBigL);
+        float4 m = f4(kNegBig);
 #pragma unroll
         for (int t = 0; t < JPL; ++t) {
             const float4 ee = cvt_raw(re[t]);
-            sv[t] = aq * kk[t] * fma4(ee, ee, ee);
+            sv[t] = score(aq, kk[t], ee);
             if (L.jok[t]) {
                 m = max4(m, sv[t]);
                 if (L.cok && s) st4_stream(sr + L.off[t], sv[t]);
@@ -146,8 +107,8 @@ __global__ __launch_bounds__(kThreads, 2) void attn_long_fwd_kernel(const T* __r
 }
 
 // column sums of one row group: straight into (dk, dv) when there is one group, else into the float32 partials
-template <typename T, int JPL, typename Lane>
-__device__ __forceinline__ void store_columns(const Lane& L, const float4* a, const float4* c, T* ka, T* va, float* part,
+template <typename T, int JPL, typename L_>
+__device__ __forceinline__ void store_columns(const L_& L, const float4* a, const float4* c, T* ka, T* va, float* part,
                                               int b, int group, int G, int B, size_t NC) {
     const size_t BNC = static_cast<size_t>(B) * NC;
 #pragma unroll
@@ -180,7 +141,7 @@ __global__ __launch_bounds__(kThreads, 2) void attn_long_bwd_kernel(
     const Place pl = place(SL, G, B, reverse);
     if (pl.b >= B) return;   // workgroup-uniform
     const int b = pl.b;
-    const LongLane<LQS, JPL> L(tid, pl.slice, N, C);
+    const Lane<kThreads, LQS, JPL> L(tid, pl.slice, N, C);
     const size_t NC = static_cast<size_t>(N) * C;
 #pragma unroll
     for (int t = 0; t < JPL; ++t) {        // each thread reads back only its own entries: no barrier
@@ -208,11 +169,11 @@ __global__ __launch_bounds__(kThreads, 2) void attn_long_bwd_kernel(
         int kl = tid;                       // opaque per row: keeps the LDS operand reads inside the loop
         asm volatile("" : "+v"(kl));
         float4 pe[JPL];
-        float4 m = f4(kNegBigL);
+        float4 m = f4(kNegBig);
 #pragma unroll
         for (int t = 0; t < JPL; ++t) {
             const float4 ee = cvt_raw(re[t]);
-            pe[t] = aq * kv[(0 * JPL + t) * kThreads + kl] * fma4(ee, ee, ee);
+            pe[t] = score(aq, kv[(0 * JPL + t) * kThreads + kl], ee);
             if (L.jok[t]) m = max4(m, pe[t]);
         }
         m = xor_max4<QS>(m);
@@ -262,10 +223,10 @@ __global__ __launch_bounds__(kThreads, 2) void attn_long_bwd_kernel(
             float4 ds = fma4(p, woi * kv[(1 * JPL + t) * kThreads + kl] - abar, ws ? cvt_raw(rws[t]) : f4(0.f));
             if (!L.jok[t]) ds = f4(0.f);
             dvv[t] = fma4(p, woi, dvv[t]);
-            const float4 dsg = ds * fma4(ee, ee, ee);
+            const float4 dsg = ds * gate(ee);
             dqa = fma4(dsg, kk, dqa);
             dkk[t] = fma4(dsg, aq, dkk[t]);
-            float4 dev = ds * aq * kk * fma4(f4(2.f), ee, f4(1.f));
+            float4 dev = ds * aq * kk * dgate(ee);
             if (ADDE) dev += cvt_raw(rae[ADDE ? t : 0]);
             if (L.jok[t] && L.cok) st4_stream(der + L.off[t], dev);
         }
@@ -305,7 +266,7 @@ __global__ __launch_bounds__(kThreads, 2) void attn_long_bwd2_kernel(
     const Place pl = place(SL, G, B, reverse);
     if (pl.b >= B) return;   // workgroup-uniform
     const int b = pl.b;
-    const LongLane<LQS, JPL> L(tid, pl.slice, N, C);
+    const Lane<kThreads, LQS, JPL> L(tid, pl.slice, N, C);
     const size_t NC = static_cast<size_t>(N) * C;
 #pragma unroll
     for (int t = 0; t < JPL; ++t) {
@@ -338,11 +299,11 @@ __global__ __launch_bounds__(kThreads, 2) void attn_long_bwd2_kernel(
         int kl = tid;
         asm volatile("" : "+v"(kl));
         float4 pe[JPL], sd[JPL];
-        float4 m = f4(kNegBigL);
+        float4 m = f4(kNegBig);
 #pragma unroll
         for (int t = 0; t < JPL; ++t) {
             const float4 ee = cvt_raw(re[t]);
-            pe[t] = aq * kv[(0 * JPL + t) * kThreads + kl] * fma4(ee, ee, ee);
+            pe[t] = score(aq, kv[(0 * JPL + t) * kThreads + kl], ee);
             if (L.jok[t]) m = max4(m, pe[t]);
         }
         m = xor_max4<QS>(m);
@@ -354,9 +315,7 @@ __global__ __launch_bounds__(kThreads, 2) void attn_long_bwd2_kernel(
             const float4 kk = kv[(0 * JPL + t) * kThreads + kl];
             const float4 vv = kv[(1 * JPL + t) * kThreads + kl];
             const float4 tkk = kv[(2 * JPL + t) * kThreads + kl];
-            const float4 g = fma4(ee, ee, ee);
-            const float4 g1 = fma4(f4(2.f), ee, f4(1.f));
-            sd[t] = alpha * (g * fma4(tqi, kk, qi * tkk) + qi * kk * g1 * cvt_raw(rte[t]));
+            sd[t] = bwd2_tangent(alpha, ee, qi, kk, tqi, tkk, rte[t]);
             if (L.jok[t] && L.cok && gws) st4_stream(gwr + L.off[t], sd[t]);
             pe[t] = L.jok[t] ? exp4(pe[t] - m) : f4(0.f);
             const float4 ps = pe[t] * sd[t];
@@ -418,9 +377,10 @@ __global__ __launch_bounds__(kThreads, 2) void attn_long_bwd2_kernel(
             const float4 tkk = kv[(2 * JPL + t) * kThreads + kl];
             const float4 tvv = kv[(3 * JPL + t) * kThreads + kl];
             const float4 p = pe[t] * scale;
+            // bwd2_slot() of attn_core.h, term for term (around the call the bf16 multi-slot instances allocate differently)
             const float4 a = woi * vv;
-            const float4 g = fma4(ee, ee, ee);
-            const float4 g1 = fma4(f4(2.f), ee, f4(1.f));
+            const float4 g = gate(ee);
+            const float4 g1 = dgate(ee);
             float4 ds = fma4(p, a - abar, ws ? cvt_raw(rws[t]) : f4(0.f));
             if (!L.jok[t]) ds = f4(0.f);
             const float4 pdot = p * (sd[t] - mm);
@@ -470,15 +430,11 @@ __global__ __launch_bounds__(256) void attn_long_colsum_kernel(const float* __re
 // ---------------------------------------------------------------- dispatch ----
 constexpr int kMaxN = 256;
 
-struct LongGeometry {
-    int lqs, jpl, slices;
-};
-
 // Slots per thread are what the registers allow without scratch (gfx950 resource report): the forward
 // keeps up to 8 (32-channel slices, N <= 256); the backward up to 4 -- above 128 neighbours it takes 16-channel slices
 // (64 phases); the second order up to 3 -- 16-channel slices up to 192 neighbours, 8-channel slices (128 phases) above.
 enum LongOp { kOpFwd, kOpBwd, kOpBwd2 };
-bool long_geometry(int N, int C, LongOp op, LongGeometry* g) {
+bool long_geometry(int N, int C, LongOp op, Geometry* g) {
     if (C < 8 || (C & 3) || N < 1 || N > kMaxN) return false;
     const int cq = C / 4;
     int lqs = (op != kOpBwd2 && cq >= 5) ? 3 : 2;
@@ -509,9 +465,11 @@ int colsum(const void* part, void* a, void* b, int B, int N, int C, int G, hipSt
     return 0;
 }
 
-#define DG_FOR_LONG_FWD(M) M(3, 2) M(3, 4) M(3, 6) M(3, 8) M(2, 1) M(2, 2) M(2, 3) M(2, 4)
-#define DG_FOR_LONG_BWD(M) M(3, 2) M(3, 4) M(2, 1) M(2, 2) M(2, 3) M(2, 4)
-#define DG_FOR_LONG_BWD2(M) M(2, 1) M(2, 2) M(2, 3) M(1, 2)
+// the instantiated (LQS, JPL)
+using LongFwd = Shapes<Shape<3, 2>, Shape<3, 4>, Shape<3, 6>, Shape<3, 8>, Shape<2, 1>, Shape<2, 2>, Shape<2, 3>, Shape<2, 4>>;
+using LongBwd = Shapes<Shape<3, 2>, Shape<3, 4>, Shape<2, 1>, Shape<2, 2>, Shape<2, 3>, Shape<2, 4>>;
+using LongBwd2 = Shapes<Shape<2, 1>, Shape<2, 2>, Shape<2, 3>, Shape<1, 2>>;
+constexpr const char* kNeed = " (need C%4==0, C>=8, 1<=N<=256)";
 
 }  // namespace
 }  // namespace dg
@@ -522,44 +480,33 @@ extern "C" size_t dg_attn_core_long_workspace_bytes(int B, int N, int C) { retur
 
 extern "C" int dg_attn_core_long_fwd(const void* q_, const void* k_, const void* v_, const void* e_, void* s_, void* o_,
                                      int B, int N, int C, float alpha, int dtype, dg_stream_t stream_) {
-    if (!q_ || !k_ || !v_ || !e_ || !o_) return fail(DG_E_ARG, "dg_attn_core_long_fwd: null pointer");  // s may be NULL
-    if (!dtype_ok(dtype)) return fail(DG_E_ARG, "dg_attn_core_long_fwd: unknown dtype %d", dtype);
-    LongGeometry g;
-    if (B < 0 || !long_geometry(N, C, kOpFwd, &g))
-        return fail(DG_E_SHAPE, "dg_attn_core_long_fwd: unsupported shape B=%d N=%d C=%d (need C%%4==0, C>=8, 1<=N<=256)",
-                    B, N, C);
+    Geometry g;
+    const bool ok = B >= 0 && long_geometry(N, C, kOpFwd, &g);
+    if (int st = check_fwd("dg_attn_core_long_fwd", q_, k_, v_, e_, o_, dtype, {ok, B, N, C, kNeed})) return st;
     if (B == 0) return 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const int G = row_groups(N, kFwdRows);
     dim3 grid(static_cast<unsigned>((B + 7) / 8 * 8) * g.slices * G), block(kThreads);
     ProfScope prof(DG_K_ATTN_FWD, stream);
     const int reverse = take_direction(static_cast<int64_t>(B) * N * N);      // per-row results: any order
-#define LAUNCH_T(T, LQS, JPL)                                                                                      \
-    hipLaunchKernelGGL((attn_long_fwd_kernel<T, LQS, JPL>), grid, block, 0, stream, static_cast<const T*>(q_),     \
-                       static_cast<const T*>(k_), static_cast<const T*>(v_), static_cast<const T*>(e_),           \
-                       static_cast<T*>(s_), static_cast<T*>(o_), N, C, alpha, g.slices, G, B, reverse);
-#define LAUNCH(LQS, JPL)                                            \
-    if (g.lqs == LQS && g.jpl == JPL) {                             \
-        if (dtype == DG_DTYPE_BF16) { LAUNCH_T(bf16_t, LQS, JPL) }  \
-        else { LAUNCH_T(float, LQS, JPL) }                          \
-    }
-    DG_FOR_LONG_FWD(LAUNCH)
-#undef LAUNCH
-#undef LAUNCH_T
-    return check_launch("dg_attn_core_long_fwd");
+    return dispatch(LongFwd(), "dg_attn_core_long_fwd", dtype, g.lqs, g.jpl, [&](auto t, auto sh) {
+        using T = decltype(t);
+        using S = decltype(sh);
+        hipLaunchKernelGGL((attn_long_fwd_kernel<T, S::LQS, S::JPL>), grid, block, 0, stream, static_cast<const T*>(q_),
+                           static_cast<const T*>(k_), static_cast<const T*>(v_), static_cast<const T*>(e_),
+                           static_cast<T*>(s_), static_cast<T*>(o_), N, C, alpha, g.slices, G, B, reverse);
+        return 0;
+    });
 }
 
 extern "C" int dg_attn_core_long_bwd(const void* q_, const void* k_, const void* v_, const void* e_, const void* ws_,
                                      const void* wo_, const void* add_e_, void* dq_, void* dk_, void* dv_, void* de_,
                                      void* workspace, size_t workspace_bytes, int B, int N, int C, float alpha,
                                      int dtype, dg_stream_t stream_) {
-    if (!q_ || !k_ || !v_ || !e_ || !wo_ || !dq_ || !dk_ || !dv_ || !de_)
-        return fail(DG_E_ARG, "dg_attn_core_long_bwd: null pointer");  // ws, add_e may be NULL
-    if (!dtype_ok(dtype)) return fail(DG_E_ARG, "dg_attn_core_long_bwd: unknown dtype %d", dtype);
-    LongGeometry g;
-    if (B < 0 || !long_geometry(N, C, kOpBwd, &g))
-        return fail(DG_E_SHAPE, "dg_attn_core_long_bwd: unsupported shape B=%d N=%d C=%d (need C%%4==0, C>=8, 1<=N<=256)",
-                    B, N, C);
+    Geometry g;
+    const bool ok = B >= 0 && long_geometry(N, C, kOpBwd, &g);
+    if (int st = check_bwd("dg_attn_core_long_bwd", q_, k_, v_, e_, wo_, dq_, dk_, dv_, de_, dtype, {ok, B, N, C, kNeed}))
+        return st;
     const size_t need = long_workspace_bytes(B, N, C);
     if (need && (!workspace || workspace_bytes < need))
         return fail(DG_E_WORKSPACE, "dg_attn_core_long_bwd: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
@@ -570,29 +517,22 @@ extern "C" int dg_attn_core_long_bwd(const void* q_, const void* k_, const void*
     ProfScope prof(DG_K_ATTN_BWD, stream);
     const int reverse = take_direction(static_cast<int64_t>(B) * N * N);      // per-group results: any order
     float* part = static_cast<float*>(workspace);
-#define LAUNCH_T(T, LQS, JPL, ADDE)                                                                                 \
-    {                                                                                                               \
-        constexpr int lds = (2 * JPL * kThreads + 2 * 4 * 4 * (1 << LQS)) * 16;                                     \
-        DG_OPT_IN_LDS((&attn_long_bwd_kernel<T, LQS, JPL, ADDE>), lds);                                              \
-        hipLaunchKernelGGL((attn_long_bwd_kernel<T, LQS, JPL, ADDE>), grid, block, lds, stream,                      \
-                           static_cast<const T*>(q_), static_cast<const T*>(k_), static_cast<const T*>(v_),         \
-                           static_cast<const T*>(e_), static_cast<const T*>(ws_), static_cast<const T*>(wo_),       \
-                           static_cast<const T*>(add_e_), static_cast<T*>(dq_), static_cast<T*>(dk_),               \
-                           static_cast<T*>(dv_), static_cast<T*>(de_), part, N, C, alpha, g.slices, G, B, reverse); \
-        if (G > 1) colsum<T>(part, dk_, dv_, B, N, C, G, stream);                                                   \
-    }
-#define LAUNCH(LQS, JPL)                                                        \
-    if (g.lqs == LQS && g.jpl == JPL) {                                         \
-        if (dtype == DG_DTYPE_BF16) {                                           \
-            if (add_e_) LAUNCH_T(bf16_t, LQS, JPL, true) else LAUNCH_T(bf16_t, LQS, JPL, false) \
-        } else {                                                                \
-            if (add_e_) LAUNCH_T(float, LQS, JPL, true) else LAUNCH_T(float, LQS, JPL, false)   \
-        }                                                                       \
-    }
-    DG_FOR_LONG_BWD(LAUNCH)
-#undef LAUNCH
-#undef LAUNCH_T
-    return check_launch("dg_attn_core_long_bwd");
+    return dispatch(LongBwd(), "dg_attn_core_long_bwd", dtype, g.lqs, g.jpl, [&](auto t, auto sh) {
+        using T = decltype(t);
+        constexpr int LQS = decltype(sh)::LQS, JPL = decltype(sh)::JPL;
+        constexpr int lds = (2 * JPL * kThreads + 2 * 4 * 4 * (1 << LQS)) * 16;
+        auto launch = [&](auto adde) {
+            constexpr bool ADDE = decltype(adde)::value;
+            DG_OPT_IN_LDS((&attn_long_bwd_kernel<T, LQS, JPL, ADDE>), lds);
+            hipLaunchKernelGGL((attn_long_bwd_kernel<T, LQS, JPL, ADDE>), grid, block, lds, stream,
+                               static_cast<const T*>(q_), static_cast<const T*>(k_), static_cast<const T*>(v_),
+                               static_cast<const T*>(e_), static_cast<const T*>(ws_), static_cast<const T*>(wo_),
+                               static_cast<const T*>(add_e_), static_cast<T*>(dq_), static_cast<T*>(dk_),
+                               static_cast<T*>(dv_), static_cast<T*>(de_), part, N, C, alpha, g.slices, G, B, reverse);
+            return G > 1 ? colsum<T>(part, dk_, dv_, B, N, C, G, stream) : 0;
+        };
+        return add_e_ ? launch(std::true_type()) : launch(std::false_type());
+    });
 }
 
 extern "C" int dg_attn_core_long_bwd2(const void* q_, const void* k_, const void* v_, const void* e_, const void* ws_,
@@ -600,13 +540,11 @@ extern "C" int dg_attn_core_long_bwd2(const void* q_, const void* k_, const void
                                       void* gq_, void* gk_, void* gv_, void* ge_, void* gws_, void* gwo_, void* workspace,
                                       size_t workspace_bytes, int B, int N, int C, float alpha, int dtype,
                                       dg_stream_t stream_) {
-    if (!q_ || !k_ || !v_ || !e_ || !wo_ || !tq_ || !tk_ || !tv_ || !te_ || !gq_ || !gk_ || !gv_ || !ge_ || !gwo_)
-        return fail(DG_E_ARG, "dg_attn_core_long_bwd2: null pointer");  // ws, gws may be NULL
-    if (!dtype_ok(dtype)) return fail(DG_E_ARG, "dg_attn_core_long_bwd2: unknown dtype %d", dtype);
-    LongGeometry g;
-    if (B < 0 || !long_geometry(N, C, kOpBwd2, &g))
-        return fail(DG_E_SHAPE, "dg_attn_core_long_bwd2: unsupported shape B=%d N=%d C=%d (need C%%4==0, C>=8, 1<=N<=256)",
-                    B, N, C);
+    Geometry g;
+    const bool ok = B >= 0 && long_geometry(N, C, kOpBwd2, &g);
+    if (int st = check_bwd2("dg_attn_core_long_bwd2", q_, k_, v_, e_, wo_, tq_, tk_, tv_, te_, gq_, gk_, gv_, ge_, gwo_, dtype,
+                            {ok, B, N, C, kNeed}))
+        return st;
     const size_t need = long_workspace_bytes(B, N, C);
     if (need && (!workspace || workspace_bytes < need))
         return fail(DG_E_WORKSPACE, "dg_attn_core_long_bwd2: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
@@ -617,26 +555,18 @@ extern "C" int dg_attn_core_long_bwd2(const void* q_, const void* k_, const void
     ProfScope prof(DG_K_ATTN_BWD2, stream);
     const int reverse = take_direction(static_cast<int64_t>(B) * N * N);      // per-group results: any order
     float* part = static_cast<float*>(workspace);
-#define LAUNCH_T(T, LQS, JPL)                                                                                       \
-    {                                                                                                               \
-        constexpr int lds = (4 * JPL * kThreads + 2 * 4 * 7 * (1 << LQS)) * 16;                                     \
-        DG_OPT_IN_LDS((&attn_long_bwd2_kernel<T, LQS, JPL>), lds);                                                   \
-        hipLaunchKernelGGL((attn_long_bwd2_kernel<T, LQS, JPL>), grid, block, lds, stream,                           \
-                           static_cast<const T*>(q_), static_cast<const T*>(k_), static_cast<const T*>(v_),         \
-                           static_cast<const T*>(e_), static_cast<const T*>(ws_), static_cast<const T*>(wo_),       \
-                           static_cast<const T*>(tq_), static_cast<const T*>(tk_), static_cast<const T*>(tv_),      \
-                           static_cast<const T*>(te_), static_cast<T*>(gq_), static_cast<T*>(gk_),                  \
-                           static_cast<T*>(gv_), static_cast<T*>(ge_), static_cast<T*>(gws_), static_cast<T*>(gwo_), \
-                           part, N, C, alpha, g.slices, G, B, reverse);                                             \
-        if (G > 1) colsum<T>(part, gk_, gv_, B, N, C, G, stream);                                                   \
-    }
-#define LAUNCH(LQS, JPL)                                        \
-    if (g.lqs == LQS && g.jpl == JPL) {                         \
-        if (dtype == DG_DTYPE_BF16) LAUNCH_T(bf16_t, LQS, JPL)  \
-        else LAUNCH_T(float, LQS, JPL)                          \
-    }
-    DG_FOR_LONG_BWD2(LAUNCH)
-#undef LAUNCH
-#undef LAUNCH_T
-    return check_launch("dg_attn_core_long_bwd2");
+    return dispatch(LongBwd2(), "dg_attn_core_long_bwd2", dtype, g.lqs, g.jpl, [&](auto t, auto sh) {
+        using T = decltype(t);
+        constexpr int LQS = decltype(sh)::LQS, JPL = decltype(sh)::JPL;
+        constexpr int lds = (4 * JPL * kThreads + 2 * 4 * 7 * (1 << LQS)) * 16;
+        DG_OPT_IN_LDS((&attn_long_bwd2_kernel<T, LQS, JPL>), lds);
+        hipLaunchKernelGGL((attn_long_bwd2_kernel<T, LQS, JPL>), grid, block, lds, stream,
+                           static_cast<const T*>(q_), static_cast<const T*>(k_), static_cast<const T*>(v_),
+                           static_cast<const T*>(e_), static_cast<const T*>(ws_), static_cast<const T*>(wo_),
+                           static_cast<const T*>(tq_), static_cast<const T*>(tk_), static_cast<const T*>(tv_),
+                           static_cast<const T*>(te_), static_cast<T*>(gq_), static_cast<T*>(gk_),
+                           static_cast<T*>(gv_), static_cast<T*>(ge_), static_cast<T*>(gws_), static_cast<T*>(gwo_),
+                           part, N, C, alpha, g.slices, G, B, reverse);
+        return G > 1 ? colsum<T>(part, gk_, gv_, B, N, C, G, stream) : 0;
+    });
 }

@@ -29,7 +29,10 @@ def _gen(shape, seed, scale=1.0):
 
 
 ATTN_SHAPES = [(2, 5, 8), (3, 6, 16), (2, 7, 12), (2, 9, 128), (1, 17, 48), (2, 24, 32), (2, 45, 128),
-               (1, 90, 128), (1, 33, 256), (3, 1, 16), (1, 96, 64)]
+               (1, 90, 128), (1, 33, 256), (3, 1, 16), (1, 96, 64),
+               # the other (LQS, JPL) families of csrc/attn_core.hip at their smallest shapes:
+               # (1, 2), (1, 3), (2, 2), (2, 3), (2, 6) in the forward and backward too, (3, 1)
+               (1, 33, 8), (1, 65, 8), (1, 17, 16), (1, 33, 12), (1, 49, 16), (2, 8, 32)]
 
 
 @pytest.mark.parametrize("B,N,C", ATTN_SHAPES)
@@ -83,7 +86,7 @@ def test_attn_core_without_score_output_and_null_ws():
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("B,N,C", [(2, 9, 128), (3, 45, 128), (1, 90, 128), (2, 7, 32)])
+@pytest.mark.parametrize("B,N,C", [(2, 9, 128), (3, 45, 128), (1, 90, 128), (2, 7, 32), (1, 33, 8), (1, 49, 16), (2, 8, 32)])
 def test_attn_core_backward_adds_an_outside_adjoint_of_e(B, N, C, dtype):
     """dg_attn_core_bwd_add: the adjoint that the gradient penalty's second order hands to the first-order pass
     (loss.py:32-47) joins de inside the kernel; dq / dk / dv are untouched, de = de(plain launch) + add_e."""

@@ -194,7 +194,7 @@ def test_long_attn_core_backward_adds_an_outside_adjoint_of_e(B, N, C, dtype):
 
 # ------------------------------------------------------------------------------- long vs short entries
 @gpu
-@pytest.mark.parametrize("B,N,C", [(3, 45, 128), (1, 90, 128), (2, 45, 12)])
+@pytest.mark.parametrize("B,N,C", [(3, 45, 128), (1, 90, 128), (2, 45, 12), (1, 33, 8), (1, 49, 16)])
 def test_long_entries_match_the_short_ones_where_both_run(B, N, C):
     from druggen_amd import functional as dgf
     alpha = 0.25
