@@ -249,7 +249,11 @@ __global__ __launch_bounds__(kThreads, 2) void attn_long_bwd_kernel(
 // Inputs of the first-order backward: (q,k,v,e,ws,wo); (tq,tk,tv,te) are the adjoints of its outputs (dq,dk,dv,de).
 // Closed form: tests/kernel_math.py::attn_core_bwd2.  Every row sum is a p-weighted sum over j, so one merge carries
 // them all: with pe = exp(s - m), l = sum pe, SV = sum pe v, SS = sum pe sd, SSV = sum pe sd v, STV = sum pe tv
-//   abar = wo SV / l,  mm = SS / l,  gwo = (SSV - mm SV + STV) / l,  sum_j p pbar = (wo (SSV + STV)) / l - 2 mm abar.
+//   abar = wo SV / l,  mm = SS / l,  gwo = (SSV - mm SV + STV) / l,
+// and the slots take pbar_j - sum_j p pbar in its centred form (sd_j - mm)(a_j - abar) + wo (tv_j - gwo): each factor is
+// one difference of like quantities.  (As pbar_j - [wo (SSV + STV) / l - 2 mm abar] the two sides round their mm a
+// products apart, and where one neighbour holds the row's weight -- pbar_j = sum_j p pbar up to exp(-gap) -- that
+// rounding was the whole result: gq, ge an order of magnitude above the one-wave kernel)
 template <typename T, int LQS, int JPL>
 __global__ __launch_bounds__(kThreads, 2) void attn_long_bwd2_kernel(
     const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, const T* __restrict__ e,
@@ -363,8 +367,8 @@ __global__ __launch_bounds__(kThreads, 2) void attn_long_bwd2_kernel(
         const float4 inv = rcp4(lt);
         const float4 abar = woi * svt * inv;
         const float4 mm = sst * inv;
-        const float4 PB = woi * (ssvt + stvt) * inv - 2.f * (mm * abar);
-        if (tid < QS && L.cok) st4(gwo + row * C + L.c0, (ssvt - mm * svt + stvt) * inv);
+        const float4 gwoi = (ssvt - mm * svt + stvt) * inv;
+        if (tid < QS && L.cok) st4(gwo + row * C + L.c0, gwoi);
         const float4 scale = fw * inv;
         T* ger = ge + row * NC;
         float4 gqa = f4(0.f);
@@ -377,15 +381,15 @@ __global__ __launch_bounds__(kThreads, 2) void attn_long_bwd2_kernel(
             const float4 tkk = kv[(2 * JPL + t) * kThreads + kl];
             const float4 tvv = kv[(3 * JPL + t) * kThreads + kl];
             const float4 p = pe[t] * scale;
-            // bwd2_slot() of attn_core.h, term for term (around the call the bf16 multi-slot instances allocate differently)
+            // bwd2_slot() of attn_core.h with sbar centred (above); around the call the bf16 multi-slot instances allocate
+            // differently
             const float4 a = woi * vv;
             const float4 g = gate(ee);
             const float4 g1 = dgate(ee);
             float4 ds = fma4(p, a - abar, ws ? cvt_raw(rws[t]) : f4(0.f));
             if (!L.jok[t]) ds = f4(0.f);
             const float4 pdot = p * (sd[t] - mm);
-            const float4 pbar = sd[t] * (a - abar) - mm * a + woi * tvv;
-            const float4 sbar = p * (pbar - PB);
+            const float4 sbar = p * fma4(sd[t] - mm, a - abar, woi * (tvv - gwoi));
             const float4 g1te = g1 * tee;
             gqa += sbar * kk * g + ds * fma4(tkk, g, kk * g1te);
             gkk[t] += sbar * aq * g + alpha * (ds * fma4(tqi, g, qi * g1te));
