@@ -155,6 +155,14 @@ def set_edge_rows(rows: int = 0) -> None:
         check(load().dg_set_edge_rows(rows), "dg_set_edge_rows")
         _edge_rows = rows
 
+# add-on entries of include/druggen_hip_embed_keep.h (same library): the edge embedding on kept signs
+EMBED_KEEP_SIGNATURES = {
+    "dg_embed_sym_sign_words": (c_size_t, [c_int, c_int]),
+    "dg_embed_sym_fwd_keep": (c_int, [_P] * 7 + [c_int] * 7 + [_P]),
+    "dg_embed_sym_bwd_keep": (c_int, [_P] * 13 + [_P, c_size_t] + [c_int] * 7 + [_P]),
+    "dg_embed_sym_bwd2_keep": (c_int, [_P] * 12 + [_P, c_size_t] + [c_int] * 7 + [_P]),
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -176,7 +184,7 @@ def load() -> ctypes.CDLL:
                 f"{LIB_PATH} not found: build it with `python -m druggen_amd.build` "
                 "(druggen_amd has no CPU / eager fallback)")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **EMBED_KEEP_SIGNATURES}.items():
             fn = getattr(lib, name)   # AttributeError if the .so lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = lib

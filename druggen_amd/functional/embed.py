@@ -89,6 +89,16 @@ def join_parts(slot, parts):
     return _JoinParts.apply(slot, *parts)
 
 
+_PIECEWISE_LINEAR = ("relu", "leaky")
+_SIGN_WORDS = 6      # uint32 words per edge row: dg_embed_sym_sign_words (128 layer-2 signs, 64 layer-1 signs)
+
+
+def _bf16_stream_bwd(out_dtype, act, E, N):
+    """The bf16 streaming backward (csrc/embed_bf16.hip) serves this first-order backward: it recomputes from ``a``."""
+    return (out_dtype == torch.bfloat16 and act in _PIECEWISE_LINEAR and E <= 8 and N <= 48
+            and options.embed_bf16 == "fast")
+
+
 class _EmbedSym(Function):
     @staticmethod
     def forward(ctx, a, w1, b1, w2, b2, act, out_dtype, slot=None):
@@ -96,43 +106,51 @@ class _EmbedSym(Function):
         B, N, _, E = a.shape
         H, C = w1.shape[0], w2.shape[0]
         out = _take_slot(slot, (B, N, N, C), out_dtype, a.device)
-        _lib.launch("dg_embed_sym_fwd", a, _lib.fptr(a), _lib.fptr(_c(w1)), _lib.fptr(_c(b1)),
-                    _lib.fptr(_embed_packed_w2(w2)), _lib.fptr(_c(b2)), _lib.ptr(out), B, N, E, H, C, _ACT_IDS[act],
-                    _lib.dt(out))
-        _account("embed_sym", B * N * N * (4 * E + out.element_size() * C), 2 * B * N * N * (E * H + H * C))
-        ctx.save_for_backward(a, w1, b1, w2, b2)
+        # relu / leaky: a forward that some backward follows keeps the signs of both pre-activations (24 B next to the
+        # 512 B of an output row) and the backward kernels read them instead of recomputing the layers.  The bf16
+        # streaming backward does not take them; its second order (the general kernel) does.
+        keep = (options.embed_keep and act in _PIECEWISE_LINEAR and any(ctx.needs_input_grad[:5])
+                and (in_second_order_forward() or not _bf16_stream_bwd(out_dtype, act, E, N)))
+        signs = torch.empty(B * N * N * _SIGN_WORDS, dtype=torch.int32, device=a.device) if keep else None
+        if keep:
+            _lib.launch("dg_embed_sym_fwd_keep", a, _lib.fptr(a), _lib.fptr(_c(w1)), _lib.fptr(_c(b1)),
+                        _lib.fptr(_embed_packed_w2(w2)), _lib.fptr(_c(b2)), _lib.ptr(out), signs.data_ptr(), B, N, E, H, C,
+                        _ACT_IDS[act], _lib.dt(out))
+        else:
+            _lib.launch("dg_embed_sym_fwd", a, _lib.fptr(a), _lib.fptr(_c(w1)), _lib.fptr(_c(b1)),
+                        _lib.fptr(_embed_packed_w2(w2)), _lib.fptr(_c(b2)), _lib.ptr(out), B, N, E, H, C, _ACT_IDS[act],
+                        _lib.dt(out))
+        _account("embed_sym", B * N * N * (4 * E + out.element_size() * C + (4 * _SIGN_WORDS if keep else 0)),
+                 2 * B * N * N * (E * H + H * C), floor=B * N * N * (4 * E + out.element_size() * C))
+        ctx.save_for_backward(a, w1, b1, w2, b2, signs)
         ctx.act = act
         ctx.out_dtype = out_dtype
         return out
 
     @staticmethod
     def backward(ctx, g):
-        a, w1, b1, w2, b2 = ctx.saved_tensors
+        a, w1, b1, w2, b2, signs = ctx.saved_tensors
         act = ctx.act
         if torch.is_grad_enabled():
             odt = ctx.out_dtype
             if act in _PIECEWISE_LINEAR:       # native second order (gradient penalty)
-                outs = _EmbedSymBwd.apply(a, w1, b1, w2, b2, g, act, odt, ctx.needs_input_grad[0],
+                outs = _EmbedSymBwd.apply(a, w1, b1, w2, b2, g, signs, act, odt, ctx.needs_input_grad[0],
                                           ctx.needs_input_grad[1] and not _inputs_only())
                 return tuple(outs) + (None, None, None)
             return _double_backward_fallback(lambda *t: _composite_embed_sym(*t, act).to(odt), (a, w1, b1, w2, b2), g) + (None, None, None)
         return _embed_bwd_launch(a, w1, b1, w2, b2, g, act, ctx.out_dtype, ctx.needs_input_grad[0],
-                                 ctx.needs_input_grad[1] and not _inputs_only()) + (None, None, None)
+                                 ctx.needs_input_grad[1] and not _inputs_only(), signs) + (None, None, None)
 
 
-_PIECEWISE_LINEAR = ("relu", "leaky")
-
-
-def _embed_bwd_launch(a, w1, b1, w2, b2, g, act, out_dtype, need_da, need_w):
+def _embed_bwd_launch(a, w1, b1, w2, b2, g, act, out_dtype, need_da, need_w, signs=None):
     B, N, _, E = a.shape
     H, C = w1.shape[0], w2.shape[0]
     lib = _lib.load()
     g = _c(g if g.dtype == out_dtype else g.to(out_dtype))
-    da = torch.empty_like(a) if need_da else None
-    dw1, db1, dw2, db2 = (torch.empty_like(t) for t in (w1, b1, w2, b2))
-    if (out_dtype == torch.bfloat16 and act in _PIECEWISE_LINEAR and E <= 8 and N <= 48
-            and options.embed_bf16 == "fast"):
+    if _bf16_stream_bwd(out_dtype, act, E, N):
         # bf16 gradients, relu / leaky: row-block streaming kernel (csrc/embed_bf16.hip)
+        da = torch.empty_like(a) if need_da else None
+        dw1, db1, dw2, db2 = (torch.empty_like(t) for t in (w1, b1, w2, b2))
         need = int(lib.dg_embed_sym_bwd_bf16_workspace_bytes(B, N))
         ws = _scratch(a, need, "embed16")
         _lib.launch("dg_embed_sym_bwd_bf16", a, _lib.fptr(a), _lib.fptr(_c(w1)), _lib.fptr(_c(b1)), _lib.fptr(_c(w2)),
@@ -143,6 +161,24 @@ def _embed_bwd_launch(a, w1, b1, w2, b2, g, act, out_dtype, need_da, need_w):
         if not need_w:
             dw1 = db1 = dw2 = db2 = None
         return da, dw1, db1, dw2, db2
+    if signs is not None:
+        # on the forward's signs (dg_embed_sym_bwd_keep): only what is wanted is allocated, computed and reduced
+        if not (need_da or need_w):
+            return None, None, None, None, None
+        da = torch.empty_like(a) if need_da else None
+        dw1, db1, dw2, db2 = (torch.empty_like(t) if need_w else None for t in (w1, b1, w2, b2))
+        ws = _scratch(a, int(lib.dg_embed_sym_workspace_bytes(B, N)), "embed") if need_w else None
+        _lib.launch("dg_embed_sym_bwd_keep", a, _lib.fptr(a), _lib.fptr(_c(w1)), _lib.fptr(_c(b1)),
+                    _lib.fptr(_embed_packed_w2(w2)), _lib.fptr(_embed_packed_w2(w2, True)), _lib.fptr(_c(b2)), _lib.ptr(g),
+                    signs.data_ptr(), _lib.ptr(da), _lib.ptr(dw1), _lib.ptr(db1), _lib.ptr(dw2), _lib.ptr(db2),
+                    ws.data_ptr() if need_w else None, ws.numel() if need_w else 0, B, N, E, H, C, _ACT_IDS[act], _lib.dt(g))
+        # reads: g, the signs, `a` for the weight gradients; writes: da.  Stages: dh always, layer 1 + dW2 + dW1 with the
+        # weight gradients, da with the input gradient
+        _account("embed_sym", B * N * N * (g.element_size() * C + 4 * _SIGN_WORDS + 4 * E * (int(need_w) + int(need_da))),
+                 2 * B * N * N * (H * C * (2 if need_w else 1) + E * H * ((2 if need_w else 0) + int(need_da))))
+        return da, dw1, db1, dw2, db2
+    da = torch.empty_like(a) if need_da else None
+    dw1, db1, dw2, db2 = (torch.empty_like(t) for t in (w1, b1, w2, b2))
     need = int(lib.dg_embed_sym_workspace_bytes(B, N))
     ws = _scratch(a, need, "embed")
     _lib.launch("dg_embed_sym_bwd", a, _lib.fptr(a), _lib.fptr(_c(w1)), _lib.fptr(_c(b1)), _lib.fptr(_embed_packed_w2(w2)),
@@ -162,26 +198,39 @@ class _EmbedSymBwd(Function):
     adjoint of ``da`` is propagated; adjoints of the parameter gradients would need the composite graph."""
 
     @staticmethod
-    def forward(ctx, a, w1, b1, w2, b2, g, act, out_dtype, need_da, need_w):
-        ctx.save_for_backward(a, w1, b1, w2, b2, g)
+    def forward(ctx, a, w1, b1, w2, b2, g, signs, act, out_dtype, need_da, need_w):
+        ctx.save_for_backward(a, w1, b1, w2, b2, g, signs)
         ctx.act, ctx.out_dtype = act, out_dtype
         outs = _embed_bwd_launch(a.detach(), w1.detach(), b1.detach(), w2.detach(), b2.detach(), g.detach(), act,
-                                 out_dtype, need_da, need_w)
+                                 out_dtype, need_da, need_w, signs)
         ctx.mark_non_differentiable(*[o for o in outs[1:] if o is not None])
         return outs
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, t_da, t_dw1, t_db1, t_dw2, t_db2):
-        a, w1, b1, w2, b2, g = ctx.saved_tensors
+        a, w1, b1, w2, b2, g, signs = ctx.saved_tensors
         if t_da is None:
-            return (None,) * 10
+            return (None,) * 11
         B, N, _, E = a.shape
         H, C = w1.shape[0], w2.shape[0]
         lib = _lib.load()
         g = _c(g if g.dtype == ctx.out_dtype else g.to(ctx.out_dtype))
         t = _c(t_da.float())
         gg = torch.empty_like(g)
+        need_w = ctx.needs_input_grad[1] and not _inputs_only()
+        if signs is not None:      # dg_embed_sym_bwd2_keep: no forward recomputation, gw1 / gw2 only when wanted
+            gw1, gw2 = (torch.empty_like(w1), torch.empty_like(w2)) if need_w else (None, None)
+            ws = _scratch(a, int(lib.dg_embed_sym_workspace_bytes(B, N)), "embed") if need_w else None
+            _lib.launch("dg_embed_sym_bwd2_keep", a, _lib.fptr(_c(a)), _lib.fptr(_c(w1)), _lib.fptr(_c(b1)),
+                        _lib.fptr(_embed_packed_w2(w2)), _lib.fptr(_embed_packed_w2(w2, True)), _lib.fptr(_c(b2)),
+                        _lib.ptr(g), _lib.fptr(t), signs.data_ptr(), _lib.ptr(gg), _lib.ptr(gw1), _lib.ptr(gw2),
+                        ws.data_ptr() if need_w else None, ws.numel() if need_w else 0, B, N, E, H, C, _ACT_IDS[ctx.act],
+                        _lib.dt(g))
+            # reads: t, the signs, g for the weight gradients; writes: gg.  Stages: q and x always, gW2 + dh + gW1 when wanted
+            _account("embed_sym", B * N * N * (4 * E + 4 * _SIGN_WORDS + g.element_size() * C * (2 if need_w else 1)),
+                     2 * B * N * N * (E * H + H * C + (2 * H * C + E * H if need_w else 0)))
+            return None, gw1, None, gw2, None, gg, None, None, None, None, None
         gw1, gw2 = torch.empty_like(w1), torch.empty_like(w2)
         need = int(lib.dg_embed_sym_workspace_bytes(B, N))
         ws = _scratch(a, need, "embed")
@@ -190,9 +239,9 @@ class _EmbedSymBwd(Function):
                     _lib.fptr(t), _lib.ptr(gg), _lib.ptr(gw1), _lib.ptr(gw2), ws.data_ptr(), ws.numel(), B, N, E, H, C,
                     _ACT_IDS[ctx.act], _lib.dt(g))
         _account("embed_sym", B * N * N * (8 * E + 2 * g.element_size() * C), 2 * B * N * N * (E * H + H * C) * 4)
-        if _inputs_only() or not ctx.needs_input_grad[1]:
+        if not need_w:
             gw1 = gw2 = None
-        return None, gw1, None, gw2, None, gg, None, None, None, None
+        return None, gw1, None, gw2, None, gg, None, None, None, None, None
 
 
 def embed_sym(a, w1, b1, w2, b2, act: str, out_dtype=torch.float32, slot=None):

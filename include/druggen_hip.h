@@ -495,6 +495,9 @@ int dg_embed_sym_bwd2(const float* a, const float* w1, const float* b1, const fl
                       void* gg, float* gw1, float* gw2, void* workspace, size_t workspace_bytes,
                       int B, int N, int E, int H, int C, int act, int dtype, dg_stream_t stream);
 
+/* The same three entries with the forward's signs KEPT instead of recomputed (relu / leaky): druggen_hip_embed_keep.h,
+ * an add-on header next to this one.  The entries above are unchanged.                                          */
+
 /* One-hot fast path of the same op (reference src/data/utils.py:15-23 makes the generator's input and the
  * discriminator's real batch one-hot): with labels l [B,N,N] (int32, 0 <= l < E) and the E x C table
  * T[c] = f(e_c) (computed and differentiated by the caller: E rows of an MLP),
