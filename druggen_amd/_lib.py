@@ -163,6 +163,11 @@ EMBED_KEEP_SIGNATURES = {
     "dg_embed_sym_bwd2_keep": (c_int, [_P] * 12 + [_P, c_size_t] + [c_int] * 7 + [_P]),
 }
 
+# add-on entry of include/druggen_hip_embed_smooth.h (same library): the embedding's second order for sigmoid / tanh
+EMBED_SMOOTH_SIGNATURES = {
+    "dg_embed_sym_bwd2_smooth": (c_int, [_P] * 14 + [_P, c_size_t] + [c_int] * 7 + [_P]),
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -184,7 +189,7 @@ def load() -> ctypes.CDLL:
                 f"{LIB_PATH} not found: build it with `python -m druggen_amd.build` "
                 "(druggen_amd has no CPU / eager fallback)")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**SIGNATURES, **EMBED_KEEP_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **EMBED_KEEP_SIGNATURES, **EMBED_SMOOTH_SIGNATURES}.items():
             fn = getattr(lib, name)   # AttributeError if the .so lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = lib

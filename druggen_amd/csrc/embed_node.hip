@@ -1,9 +1,10 @@
 // Node embedding of Generator / Discriminator (reference src/model/models.py:52-56, 154-158, applied at :91 / :196):
 //     a1 = act(z W1^T + b1) [R,64] ;  a2 = act(a1 W2^T + b2) [R,128]          Linear(E,64) - act - Linear(64,128) - act
 // over the R = B N node rows.  On the BLAS + ATen: 4 launches forward, ~8 backward, ~8 in the gradient penalty's second order,
-// for 9 k multiply-adds per row.  Two kernels for the piecewise-linear activations (ReLU, LeakyReLU(0.01): act'' = 0):
+// for 9 k multiply-adds per row.  Two kernels; forward and first backward for all four activations, the second-order form for
+// the piecewise-linear ones (ReLU, LeakyReLU(0.01): act'' = 0) only:
 //   embed_node_chain   both layers for 32 rows per workgroup.  Forward: activations from the pre-activations.  Second order
-//                      (`m1`, `m2` = the forward's a1, a2; `in` = t, the adjoint of the first backward's dz):
+//                      (`m1`, `m2` = the forward's a1, a2; `in` = t, the adjoint of the first backward's dz; relu / leaky):
 //                      u1 = (t W1^T) . act'(a1), u2 = (u1 W2^T) . act'(a2) -- the adjoints of g2 W2 and of the upstream gradient.
 //   embed_node_bwd     g2 = g . act'(a2), g1 = (g2 W2) . act'(a1), dz = g1 W1 (optional).
 // The parameter gradients (g2^T a1, g1^T z and their second-order twins g2^T u1, g1^T t) stay dg_linear_wgrad's.
@@ -16,14 +17,24 @@ constexpr int kH = 64, kC = 128, kEP = 16;      // hidden width, output width, p
 constexpr int kRowsN = 32;
 constexpr int kS1 = kH + 1, kS2 = kC + 1;       // strides of the transposed weights in LDS
 
-enum NodeAct { kNodeRelu = 0, kNodeLeaky = 1 };
+enum NodeAct { kNodeRelu = 0, kNodeLeaky = 1, kNodeSigmoid = 2, kNodeTanh = 3 };      // the ids of dg_embed_sym_*
 template <int ACT>
 __device__ __forceinline__ float node_act(float x) {
-    return ACT == kNodeRelu ? fmaxf(x, 0.f) : (x > 0.f ? x : 0.01f * x);
+    switch (ACT) {
+        case kNodeRelu: return fmaxf(x, 0.f);
+        case kNodeLeaky: return x > 0.f ? x : 0.01f * x;
+        case kNodeSigmoid: return 1.0f / (1.0f + __expf(-x));
+        default: return tanhf(x);
+    }
 }
 template <int ACT>
 __device__ __forceinline__ float node_dact(float a) {      // through the OUTPUT a = act(x)
-    return a > 0.f ? 1.f : (ACT == kNodeRelu ? 0.f : 0.01f);
+    switch (ACT) {
+        case kNodeRelu: return a > 0.f ? 1.f : 0.f;
+        case kNodeLeaky: return a > 0.f ? 1.f : 0.01f;
+        case kNodeSigmoid: return a * (1.f - a);
+        default: return 1.f - a * a;
+    }
 }
 
 template <int ACT, bool MASKED>
@@ -199,9 +210,13 @@ __global__ __launch_bounds__(256) void embed_node_bwd_kernel(const float* __rest
     }
 }
 
-int node_check(const char* who, int64_t R, int E, int act) {
+// `masked`: the second-order form of the chain, "the same chain with a mask" only where act'' = 0
+int node_check(const char* who, int64_t R, int E, int act, bool masked = false) {
     if (R < 0 || E < 1 || E > kEP) return fail(DG_E_SHAPE, "%s: unsupported shape R=%lld E=%d (1 <= E <= 16)", who, static_cast<long long>(R), E);
-    if (act != kNodeRelu && act != kNodeLeaky) return fail(DG_E_ARG, "%s: activation %d (0 relu, 1 leaky relu 0.01)", who, act);
+    if (act < kNodeRelu || act > kNodeTanh)
+        return fail(DG_E_ARG, "%s: activation %d (0 relu, 1 leaky relu 0.01, 2 sigmoid, 3 tanh)", who, act);
+    if (masked && act != kNodeRelu && act != kNodeLeaky)
+        return fail(DG_E_ARG, "%s: the second-order (masked) form is for relu / leaky relu only, got activation %d", who, act);
     return 0;
 }
 
@@ -217,13 +232,16 @@ extern "C" int dg_embed_node_chain(const float* in, const float* m1, const float
     if (!in || !w1 || !w2 || !o1 || !o2) return fail(DG_E_ARG, "dg_embed_node_chain: null pointer");
     if ((m1 != nullptr) != (m2 != nullptr))
         return fail(DG_E_ARG, "dg_embed_node_chain: m1 and m2 are given together (second order) or not at all (forward)");
-    if (int st = node_check("dg_embed_node_chain", R, E, act)) return st;
+    if (int st = node_check("dg_embed_node_chain", R, E, act, m1 != nullptr)) return st;
     if (R == 0) return 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const dim3 grid(static_cast<unsigned>((R + kRowsN - 1) / kRowsN));
 #define LAUNCH(A, M) hipLaunchKernelGGL((embed_node_chain_kernel<A, M>), grid, dim3(256), 0, stream, in, m1, m2, w1, b1, w2, b2, o1, o2, R, E)
     if (m1) { if (act == kNodeRelu) LAUNCH(kNodeRelu, true); else LAUNCH(kNodeLeaky, true); }
-    else { if (act == kNodeRelu) LAUNCH(kNodeRelu, false); else LAUNCH(kNodeLeaky, false); }
+    else if (act == kNodeRelu) LAUNCH(kNodeRelu, false);
+    else if (act == kNodeLeaky) LAUNCH(kNodeLeaky, false);
+    else if (act == kNodeSigmoid) LAUNCH(kNodeSigmoid, false);
+    else LAUNCH(kNodeTanh, false);
 #undef LAUNCH
     return check_launch("dg_embed_node_chain");
 }
@@ -235,7 +253,11 @@ extern "C" int dg_embed_node_bwd(const float* g, const float* a1, const float* a
     if (R == 0) return 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const dim3 grid(static_cast<unsigned>((R + kRowsN - 1) / kRowsN));
-    if (act == kNodeRelu) hipLaunchKernelGGL((embed_node_bwd_kernel<kNodeRelu>), grid, dim3(256), 0, stream, g, a1, a2, w1, w2, g2, g1, dz, R, E);
-    else hipLaunchKernelGGL((embed_node_bwd_kernel<kNodeLeaky>), grid, dim3(256), 0, stream, g, a1, a2, w1, w2, g2, g1, dz, R, E);
+#define LAUNCH(A) hipLaunchKernelGGL((embed_node_bwd_kernel<A>), grid, dim3(256), 0, stream, g, a1, a2, w1, w2, g2, g1, dz, R, E)
+    if (act == kNodeRelu) LAUNCH(kNodeRelu);
+    else if (act == kNodeLeaky) LAUNCH(kNodeLeaky);
+    else if (act == kNodeSigmoid) LAUNCH(kNodeSigmoid);
+    else LAUNCH(kNodeTanh);
+#undef LAUNCH
     return check_launch("dg_embed_node_bwd");
 }

@@ -40,6 +40,17 @@ __device__ __forceinline__ float act_grad_from_output(float y) {
         default: return 1.f - y * y;
     }
 }
+// first and second derivative through the OUTPUT y (embed_sym_smooth.hip); zero curvature for the piecewise-linear ones
+template <int act>
+__device__ __forceinline__ void act_grad2_from_output(float y, float* d1, float* d2) {
+    const float d = act_grad_from_output<act>(y);
+    *d1 = d;
+    switch (act) {
+        case kSigmoid: *d2 = d * fmaf(-2.f, y, 1.f); break;
+        case kTanh: *d2 = -2.f * y * d; break;
+        default: *d2 = 0.f;
+    }
+}
 
 struct PairTile {
     int b;        // molecule

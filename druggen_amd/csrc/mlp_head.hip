@@ -3,7 +3,7 @@
 // over B (or 2B) rows -- on the BLAS + ATen that is 6 launches forward, 13 backward and ~20 in the second order of the
 // gradient penalty, each a few microseconds of launch for a few thousand multiply-adds.  Three kernels cover all of it for the
 // piecewise-linear activations (ReLU, LeakyReLU(0.01): act'' = 0, so the second order is the same chain with the forward's
-// activation pattern as a mask):
+// activation pattern as a mask); sigmoid / tanh take the forward and the first backward, their second order is refused:
 //   head_chain   rows through the three layers.  Forward: activations from the pre-activations.  Second order (`m1` given):
 //                u1 = t . act'(a1), u2 = (u1 W2^T) . act'(a2), u3 = (u2 W3^T) . act'(a3), u_out = u3 W4^T  -- the adjoints of
 //                g2 W2, g3 W3, g_out W4 and g_out when t is the adjoint of the first backward's result.
@@ -19,16 +19,26 @@ namespace {
 
 constexpr int kW1 = 64, kW2 = 32, kW3 = 16;
 
-enum HeadAct { kHeadRelu = 0, kHeadLeaky = 1 };
+enum HeadAct { kHeadRelu = 0, kHeadLeaky = 1, kHeadSigmoid = 2, kHeadTanh = 3 };      // the ids of dg_embed_sym_*
 
 template <int ACT>
 __device__ __forceinline__ float head_act(float x) {
-    return ACT == kHeadRelu ? fmaxf(x, 0.f) : (x > 0.f ? x : 0.01f * x);
+    switch (ACT) {
+        case kHeadRelu: return fmaxf(x, 0.f);
+        case kHeadLeaky: return x > 0.f ? x : 0.01f * x;
+        case kHeadSigmoid: return 1.0f / (1.0f + __expf(-x));
+        default: return tanhf(x);
+    }
 }
-// derivative through the OUTPUT a = act(x) (a > 0 exactly when x > 0 for both activations)
+// derivative through the OUTPUT a = act(x) (relu / leaky: a > 0 exactly when x > 0)
 template <int ACT>
 __device__ __forceinline__ float head_dact(float a) {
-    return a > 0.f ? 1.f : (ACT == kHeadRelu ? 0.f : 0.01f);
+    switch (ACT) {
+        case kHeadRelu: return a > 0.f ? 1.f : 0.f;
+        case kHeadLeaky: return a > 0.f ? 1.f : 0.01f;
+        case kHeadSigmoid: return a * (1.f - a);
+        default: return 1.f - a * a;
+    }
 }
 
 struct HeadWeights {
@@ -230,9 +240,13 @@ __global__ __launch_bounds__(1024) void head_wgrad_kernel(const float* __restric
     }
 }
 
-int head_check(const char* who, int64_t R, int act) {
+// `masked`: the second-order form of the chain, "the same chain with a mask" only where act'' = 0
+int head_check(const char* who, int64_t R, int act, bool masked = false) {
     if (R < 0) return fail(DG_E_SHAPE, "%s: negative row count", who);
-    if (act != kHeadRelu && act != kHeadLeaky) return fail(DG_E_ARG, "%s: activation %d (0 relu, 1 leaky relu 0.01)", who, act);
+    if (act < kHeadRelu || act > kHeadTanh)
+        return fail(DG_E_ARG, "%s: activation %d (0 relu, 1 leaky relu 0.01, 2 sigmoid, 3 tanh)", who, act);
+    if (masked && act != kHeadRelu && act != kHeadLeaky)
+        return fail(DG_E_ARG, "%s: the second-order (masked) form is for relu / leaky relu only, got activation %d", who, act);
     return 0;
 }
 
@@ -248,14 +262,17 @@ extern "C" int dg_head_chain(const float* in, const float* m1, const float* m2, 
     if (!in || !w2 || !w3 || !w4 || !o1 || !o2 || !o3 || !o4) return fail(DG_E_ARG, "dg_head_chain: null pointer");
     if ((m1 != nullptr) != (m2 != nullptr) || (m1 != nullptr) != (m3 != nullptr))
         return fail(DG_E_ARG, "dg_head_chain: m1, m2, m3 are given together (second order) or not at all (forward)");
-    if (int st = head_check("dg_head_chain", R, act)) return st;
+    if (int st = head_check("dg_head_chain", R, act, m1 != nullptr)) return st;
     if (R == 0) return 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const HeadWeights w{w2, m1 ? nullptr : b2, w3, m1 ? nullptr : b3, w4, m1 ? nullptr : b4};
     const dim3 grid(static_cast<unsigned>((R + kRows - 1) / kRows));
 #define LAUNCH(A, M) hipLaunchKernelGGL((head_chain_kernel<A, M>), grid, dim3(256), 0, stream, in, m1, m2, m3, w, o1, o2, o3, o4, R)
     if (m1) { if (act == kHeadRelu) LAUNCH(kHeadRelu, true); else LAUNCH(kHeadLeaky, true); }
-    else { if (act == kHeadRelu) LAUNCH(kHeadRelu, false); else LAUNCH(kHeadLeaky, false); }
+    else if (act == kHeadRelu) LAUNCH(kHeadRelu, false);
+    else if (act == kHeadLeaky) LAUNCH(kHeadLeaky, false);
+    else if (act == kHeadSigmoid) LAUNCH(kHeadSigmoid, false);
+    else LAUNCH(kHeadTanh, false);
 #undef LAUNCH
     return check_launch("dg_head_chain");
 }
@@ -268,8 +285,12 @@ extern "C" int dg_head_bwd(const float* g_out, const float* a1, const float* a2,
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const HeadWeights w{w2, nullptr, w3, nullptr, w4, nullptr};
     const dim3 grid(static_cast<unsigned>((R + kRows - 1) / kRows));
-    if (act == kHeadRelu) hipLaunchKernelGGL((head_bwd_kernel<kHeadRelu>), grid, dim3(256), 0, stream, g_out, a1, a2, a3, w, g3, g2, g1, R);
-    else hipLaunchKernelGGL((head_bwd_kernel<kHeadLeaky>), grid, dim3(256), 0, stream, g_out, a1, a2, a3, w, g3, g2, g1, R);
+#define LAUNCH(A) hipLaunchKernelGGL((head_bwd_kernel<A>), grid, dim3(256), 0, stream, g_out, a1, a2, a3, w, g3, g2, g1, R)
+    if (act == kHeadRelu) LAUNCH(kHeadRelu);
+    else if (act == kHeadLeaky) LAUNCH(kHeadLeaky);
+    else if (act == kHeadSigmoid) LAUNCH(kHeadSigmoid);
+    else LAUNCH(kHeadTanh);
+#undef LAUNCH
     return check_launch("dg_head_bwd");
 }
 

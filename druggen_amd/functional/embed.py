@@ -9,7 +9,7 @@ from torch.autograd.function import once_differentiable
 from .. import _lib
 from ..options import options
 from ._runtime import _account, _c, in_second_order_forward, _inputs_only, PackCache, _scratch
-from .dense import _double_backward_fallback, linear
+from .dense import linear
 
 
 # --------------------------------------------------------------------------
@@ -137,7 +137,10 @@ class _EmbedSym(Function):
                 outs = _EmbedSymBwd.apply(a, w1, b1, w2, b2, g, signs, act, odt, ctx.needs_input_grad[0],
                                           ctx.needs_input_grad[1] and not _inputs_only())
                 return tuple(outs) + (None, None, None)
-            return _double_backward_fallback(lambda *t: _composite_embed_sym(*t, act).to(odt), (a, w1, b1, w2, b2), g) + (None, None, None)
+            # smooth activations: the general first backward as a node whose backward is dg_embed_sym_bwd2_smooth
+            outs = _EmbedSymBwdSmooth.apply(a, w1, b1, w2, b2, g, act, odt, ctx.needs_input_grad[0],
+                                            ctx.needs_input_grad[1] and not _inputs_only())
+            return tuple(outs) + (None, None, None)
         return _embed_bwd_launch(a, w1, b1, w2, b2, g, act, ctx.out_dtype, ctx.needs_input_grad[0],
                                  ctx.needs_input_grad[1] and not _inputs_only(), signs) + (None, None, None)
 
@@ -193,8 +196,8 @@ def _embed_bwd_launch(a, w1, b1, w2, b2, g, act, out_dtype, need_da, need_w, sig
 
 
 class _EmbedSymBwd(Function):
-    """First backward of ``_EmbedSym`` as a differentiable node (piecewise-linear activations): its own backward is
-    ``dg_embed_sym_bwd2`` -- the gradient penalty differentiates d out / d a (reference loss.py:32-39).  Only the
+    """First backward of ``_EmbedSym`` as a differentiable node (piecewise-linear activations; ``_EmbedSymBwdSmooth`` is
+    the node of sigmoid / tanh): its own backward is ``dg_embed_sym_bwd2`` -- the gradient penalty differentiates d out / d a (reference loss.py:32-39).  Only the
     adjoint of ``da`` is propagated; adjoints of the parameter gradients would need the composite graph."""
 
     @staticmethod
@@ -244,6 +247,51 @@ class _EmbedSymBwd(Function):
         return None, gw1, None, gw2, None, gg, None, None, None, None, None
 
 
+class _EmbedSymBwdSmooth(Function):
+    """First backward of ``_EmbedSym`` as a differentiable node for sigmoid / tanh: the general ``dg_embed_sym_bwd``, whose
+    own backward is ``dg_embed_sym_bwd2_smooth``.  With act'' != 0 the adjoint of ``da`` reaches every operand: ``a``, the
+    four parameters and ``g``.  As in ``_EmbedSymBwd`` only the adjoint of ``da`` is propagated."""
+
+    @staticmethod
+    def forward(ctx, a, w1, b1, w2, b2, g, act, out_dtype, need_da, need_w):
+        ctx.save_for_backward(a, w1, b1, w2, b2, g)
+        ctx.act, ctx.out_dtype = act, out_dtype
+        outs = _embed_bwd_launch(a.detach(), w1.detach(), b1.detach(), w2.detach(), b2.detach(), g.detach(), act,
+                                 out_dtype, need_da, need_w)
+        ctx.mark_non_differentiable(*[o for o in outs[1:] if o is not None])
+        return outs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, t_da, t_dw1, t_db1, t_dw2, t_db2):
+        a, w1, b1, w2, b2, g = ctx.saved_tensors
+        if t_da is None:
+            return (None,) * 10
+        B, N, _, E = a.shape
+        H, C = w1.shape[0], w2.shape[0]
+        lib = _lib.load()
+        g = _c(g if g.dtype == ctx.out_dtype else g.to(ctx.out_dtype))
+        t = _c(t_da.float())
+        gg = torch.empty_like(g)
+        need_a = ctx.needs_input_grad[0]
+        need_w = any(ctx.needs_input_grad[1:5]) and not _inputs_only()
+        ga = torch.empty_like(a) if need_a else None
+        gw1, gb1, gw2, gb2 = (torch.empty_like(p) if need_w else None for p in (w1, b1, w2, b2))
+        ws = _scratch(a, int(lib.dg_embed_sym_workspace_bytes(B, N)), "embed") if need_w else None
+        _lib.launch("dg_embed_sym_bwd2_smooth", a, _lib.fptr(_c(a)), _lib.fptr(_c(w1)), _lib.fptr(_c(b1)),
+                    _lib.fptr(_embed_packed_w2(w2)), _lib.fptr(_embed_packed_w2(w2, True)), _lib.fptr(_c(b2)), _lib.ptr(g),
+                    _lib.fptr(t), _lib.ptr(gg), _lib.fptr(ga), _lib.fptr(gw1), _lib.fptr(gb1), _lib.fptr(gw2), _lib.fptr(gb2),
+                    ws.data_ptr() if need_w else None, ws.numel() if need_w else 0, B, N, E, H, C, _ACT_IDS[ctx.act],
+                    _lib.dt(g))
+        # reads: a, t, g; writes: gg and, when wanted, ga.  Stages: both layers, q and two layer-2 passes always; the two dh
+        # passes and W1 t again for ga or the parameters; two dW2 and two dW1 stages for the parameters; W1^T r1 for ga
+        rest = need_a or need_w
+        _account("embed_sym", B * N * N * (4 * E * (3 if need_a else 2) + 2 * g.element_size() * C),
+                 2 * B * N * N * (2 * E * H + 2 * H * C + (2 * H * C + E * H if rest else 0)
+                                  + (2 * H * C + 2 * E * H if need_w else 0) + (E * H if need_a else 0)))
+        return ga, gw1, gb1, gw2, gb2, gg, None, None, None, None
+
+
 def embed_sym(a, w1, b1, w2, b2, act: str, out_dtype=torch.float32, slot=None):
     """(f(a) + f(a)^T(i<->j)) / 2 with f = act(W2 act(W1 a + b1) + b2): the edge embedding MLP and the
     symmetrisation of Generator / Discriminator in one kernel per direction (hidden 64, dim 128).
@@ -251,7 +299,7 @@ def embed_sym(a, w1, b1, w2, b2, act: str, out_dtype=torch.float32, slot=None):
     ok = (a.is_cuda and a.dtype == torch.float32 and a.dim() == 4 and a.shape[1] == a.shape[2] and act in _ACT_IDS
           and a.shape[-1] <= 16 and tuple(w1.shape) == (64, a.shape[-1]) and tuple(w2.shape) == (128, 64)
           and b1 is not None and b2 is not None)
-    if not ok or (in_second_order_forward() and act not in _PIECEWISE_LINEAR):
+    if not ok:
         out = _composite_embed_sym(a, w1, b1, w2, b2, act).to(out_dtype)
         if slot is not None:
             slot.tensor = None          # the caller falls back to a concatenation

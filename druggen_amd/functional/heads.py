@@ -7,7 +7,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from .. import _lib
-from ._runtime import _account, _c, _inputs_only, _scratch
+from ._runtime import _account, _c, in_second_order_forward, _inputs_only, _scratch
 from .dense import _double_backward_fallback, linear, _wgrad
 
 
@@ -55,14 +55,25 @@ class _Readout(Function):
         return (None if dx is None else dx.view(x.shape)), dw, db
 
 
-_HEAD_ACTS = {"relu": 0, "leaky": 1}
+_HEAD_ACTS = {"relu": 0, "leaky": 1, "sigmoid": 2, "tanh": 3}
+_SMOOTH_ACT_FNS = {2: torch.sigmoid, 3: torch.tanh}      # first order on the chain kernels; a second order takes the composite
+
+
+def _composite_node_embed(z, w1, b1, w2, b2, act):
+    f = _SMOOTH_ACT_FNS[act]
+    return f(linear(f(linear(z, w1, b1)), w2, b2))
+
+
+def _composite_head_tail(z1, w2, b2, w3, b3, w4, b4, act):
+    f, lin = _SMOOTH_ACT_FNS[act], torch.nn.functional.linear
+    return lin(f(lin(f(lin(f(z1), w2, b2)), w3, b3)), w4, b4)
 
 
 class _NodeEmbed(Function):
     """Linear(E, 64) - act - Linear(64, 128) - act over the node rows (reference models.py:52-56, 154-158) as ONE launch
     (dg_embed_node_chain); backward: one launch for g2 / g1 / dz (dg_embed_node_bwd) + the two weight gradients on
     dg_linear_wgrad; differentiable again (``_NodeEmbedBwd``: the penalty's second order is the chain kernel with the
-    activation pattern as a mask)."""
+    activation pattern as a mask; sigmoid / tanh, act'' != 0: the composite graph)."""
 
     @staticmethod
     def forward(ctx, z, w1, b1, w2, b2, act):
@@ -73,13 +84,17 @@ class _NodeEmbed(Function):
         a2 = torch.empty(R, 128, dtype=torch.float32, device=z.device)
         _lib.launch("dg_embed_node_chain", z2, _lib.ptr(z2), None, None, _lib.fptr(_c(w1)), _lib.fptr(_c(b1)),
                     _lib.fptr(_c(w2)), _lib.fptr(_c(b2)), _lib.ptr(a1), _lib.ptr(a2), R, E, act)
-        ctx.save_for_backward(z2, a1, a2, w1, w2)
+        ctx.save_for_backward(z2, a1, a2, w1, w2, *((z, b1, b2) if act in _SMOOTH_ACT_FNS else ()))
         ctx.act, ctx.zshape = act, z.shape
         return a2.view(*z.shape[:-1], 128)
 
     @staticmethod
     def backward(ctx, g):
-        z2, a1, a2, w1, w2 = ctx.saved_tensors
+        z2, a1, a2, w1, w2 = ctx.saved_tensors[:5]
+        if ctx.act in _SMOOTH_ACT_FNS and torch.is_grad_enabled():
+            z, b1, b2 = ctx.saved_tensors[5:]
+            act = ctx.act
+            return _double_backward_fallback(lambda *t: _composite_node_embed(*t, act), (z, w1, b1, w2, b2), g) + (None,)
         need_w = any(ctx.needs_input_grad[1:5]) and not _inputs_only()
         dz, dw1, db1, dw2, db2 = _NodeEmbedBwd.apply(g, z2, a1, a2, w1, w2, ctx.needs_input_grad[0], need_w, ctx.act)
         return (None if dz is None else dz.view(ctx.zshape)), dw1, db1, dw2, db2, None
@@ -129,8 +144,14 @@ class _NodeEmbedBwd(Function):
         return u2.view(ctx.gshape), None, None, None, gw1, gw2, None, None, None
 
 
+def _chain_act_ok(act_name) -> bool:
+    """relu / leaky in every order; sigmoid / tanh outside ``second_order_forward()`` only (the chains' second order is the
+    masked form, act'' = 0)."""
+    return act_name in _HEAD_ACTS and not (_HEAD_ACTS[act_name] in _SMOOTH_ACT_FNS and in_second_order_forward())
+
+
 def node_embed_supported(z, l1, l2, act_name) -> bool:
-    return (z.is_cuda and z.dtype == torch.float32 and act_name in _HEAD_ACTS and 1 <= z.shape[-1] <= 16
+    return (z.is_cuda and z.dtype == torch.float32 and _chain_act_ok(act_name) and 1 <= z.shape[-1] <= 16
             and tuple(l1.weight.shape) == (64, z.shape[-1]) and tuple(l2.weight.shape) == (128, 64)
             and l1.bias is not None and l2.bias is not None and l1.weight.dtype == torch.float32)
 
@@ -144,11 +165,12 @@ class _HeadTail(Function):
     """Tail of the Discriminator head after its first Linear (reference models.py:173-178, 207): act - Linear(64, 32) - act -
     Linear(32, 16) - act - Linear(16, 1) over the rows of ``z1`` as ONE launch (dg_head_chain); the backward is one launch
     for the input gradient (dg_head_bwd) and one for the six parameter gradients (dg_head_wgrad), itself differentiable
-    (``_HeadTailBwd``: the gradient penalty's second order is the same chain kernel with the activation pattern as a mask)."""
+    (``_HeadTailBwd``: the gradient penalty's second order is the same chain kernel with the activation pattern as a mask;
+    sigmoid / tanh, act'' != 0: the composite graph)."""
 
     @staticmethod
     def forward(ctx, z1, w2, b2, w3, b3, w4, b4, act):
-        z1 = _c(z1)
+        z_in, z1 = z1, _c(z1)
         R = z1.shape[0]
         dev = z1.device
         a1, a2, a3 = (torch.empty(R, n, dtype=torch.float32, device=dev) for n in (64, 32, 16))
@@ -156,13 +178,18 @@ class _HeadTail(Function):
         _lib.launch("dg_head_chain", z1, _lib.ptr(z1), None, None, None, _lib.fptr(_c(w2)), _lib.fptr(_c(b2)),
                     _lib.fptr(_c(w3)), _lib.fptr(_c(b3)), _lib.fptr(_c(w4)), _lib.fptr(_c(b4)), _lib.ptr(a1), _lib.ptr(a2),
                     _lib.ptr(a3), _lib.ptr(out), R, act)
-        ctx.save_for_backward(a1, a2, a3, w2, w3, w4)
+        ctx.save_for_backward(a1, a2, a3, w2, w3, w4, *((z_in, b2, b3, b4) if act in _SMOOTH_ACT_FNS else ()))
         ctx.act = act
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        a1, a2, a3, w2, w3, w4 = ctx.saved_tensors
+        a1, a2, a3, w2, w3, w4 = ctx.saved_tensors[:6]
+        if ctx.act in _SMOOTH_ACT_FNS and torch.is_grad_enabled():
+            z1, b2, b3, b4 = ctx.saved_tensors[6:]
+            act = ctx.act
+            return _double_backward_fallback(lambda *t: _composite_head_tail(*t, act), (z1, w2, b2, w3, b3, w4, b4),
+                                             g_out) + (None,)
         need_w = any(ctx.needs_input_grad[1:7]) and not _inputs_only()
         g1, dw2, db2, dw3, db3, dw4, db4 = _HeadTailBwd.apply(g_out, a1, a2, a3, w2, w3, w4, need_w, ctx.act)
         return g1, dw2, db2, dw3, db3, dw4, db4, None
@@ -217,7 +244,7 @@ class _HeadTailBwd(Function):
 
 def head_tail_supported(z1, layers, act_name) -> bool:
     """``layers`` = the three Linears after the head's first one."""
-    return (z1.is_cuda and z1.dtype == torch.float32 and z1.dim() == 2 and act_name in _HEAD_ACTS
+    return (z1.is_cuda and z1.dtype == torch.float32 and z1.dim() == 2 and _chain_act_ok(act_name)
             and [tuple(l.weight.shape) for l in layers] == [(32, 64), (16, 32), (1, 16)]
             and all(l.bias is not None and l.weight.dtype == torch.float32 for l in layers))
 

@@ -497,6 +497,8 @@ int dg_embed_sym_bwd2(const float* a, const float* w1, const float* b1, const fl
 
 /* The same three entries with the forward's signs KEPT instead of recomputed (relu / leaky): druggen_hip_embed_keep.h,
  * an add-on header next to this one.  The entries above are unchanged.                                          */
+/* The second order for the smooth activations (sigmoid / tanh, act'' != 0: dg_embed_sym_bwd2_smooth):
+ * druggen_hip_embed_smooth.h, an add-on header next to this one.                                                */
 
 /* One-hot fast path of the same op (reference src/data/utils.py:15-23 makes the generator's input and the
  * discriminator's real batch one-hot): with labels l [B,N,N] (int32, 0 <= l < E) and the E x C table
@@ -568,8 +570,8 @@ int dg_skinny_linear_wgrad(const float* dy, const void* x, float* dw, float* db,
 
 /* Tail of the Discriminator head (reference models.py:173-178, 207: node_mlp after its first Linear): rows [R,64] of
  * pre-activations z1 -> a1 = act(z1) [R,64], a2 = act(a1 W2^T + b2) [R,32], a3 = act(a2 W3^T + b3) [R,16], out = a3 W4^T + b4
- * [R,1] in ONE launch (6 on the BLAS + ATen).  w2 [32,64], w3 [16,32], w4 [1,16], float32; act: 0 ReLU, 1 LeakyReLU(0.01)
- * (other activations: not served, the caller keeps torch.nn.Sequential).
+ * [R,1] in ONE launch (6 on the BLAS + ATen).  w2 [32,64], w3 [16,32], w4 [1,16], float32; act: 0 ReLU, 1 LeakyReLU(0.01),
+ * 2 Sigmoid, 3 Tanh (forward and dg_head_bwd; the second-order form below is for act 0 / 1 only, act 2 / 3: DG_E_ARG).
  *   dg_head_chain, m1 = m2 = m3 = NULL: the forward (o1..o4 = a1, a2, a3, out).
  *   dg_head_chain, m1..m3 = a1..a3 (the forward's activations), `in` = t [R,64]: the second order of the gradient penalty --
  *     o1 = t . act'(a1), o2 = (o1 W2^T) . act'(a2), o3 = (o2 W3^T) . act'(a3), o4 = o3 W4^T (biases unused); with t the
@@ -588,7 +590,8 @@ int dg_head_wgrad(const float* l4, const float* r4, const float* l3, const float
                   float* dw4, float* db4, float* dw3, float* db3, float* dw2, float* db2, int64_t R, dg_stream_t stream);
 
 /* Node embedding (reference models.py:52-56, 154-158: node_layers = Linear(E, 64) - act - Linear(64, 128) - act - Dropout,
- * applied at :91 / :196) over the R = B N node rows, float32, E <= 16; act: 0 ReLU, 1 LeakyReLU(0.01).
+ * applied at :91 / :196) over the R = B N node rows, float32, E <= 16; act: 0 ReLU, 1 LeakyReLU(0.01), 2 Sigmoid,
+ * 3 Tanh (forward and dg_embed_node_bwd; the second-order form below is for act 0 / 1 only, act 2 / 3: DG_E_ARG).
  *   dg_embed_node_chain, m1 = m2 = NULL: o1 = act(in W1^T + b1) [R,64], o2 = act(o1 W2^T + b2) [R,128] in one launch.
  *   dg_embed_node_chain, m1 / m2 = the forward's o1 / o2, `in` = t [R,E]: the gradient penalty's second order --
  *     o1 = (t W1^T) . act'(m1), o2 = (o1 W2^T) . act'(m2) (biases unused): with t the adjoint of dg_embed_node_bwd's dz, o2 is
