@@ -22,8 +22,6 @@
 #include "traversal.h"
 
 namespace dg {
-bool reduce_batch_try_add(const float* part, int S, long long n_floats, float* out);      // linear_wgrad.hip
-void launch_ln_finish(const float* part, int nblocks, int K, int C, float* out0, float* out1, hipStream_t stream);
 namespace {
 
 constexpr int kNP = 48;                                   // rows of a stage (row groups are padded to 48 rows)

@@ -17,6 +17,16 @@ char* error_buffer();
 int fail(int code, const char* fmt, ...);
 int check_launch(const char* what);
 
+// ---- host helpers that several translation units call ----------------------------
+// out_k[c] = sum_b part[b][k][c] in a fixed order (layernorm.hip)
+void launch_ln_finish(const float* part, int nblocks, int K, int C, float* out0, float* out1, hipStream_t stream);
+// out[i] = sum_s part[s][i] over float4 columns, fixed order (linear_wgrad.hip)
+void launch_splitk_reduce(const float* part, int S, int64_t n4, float* out, hipStream_t stream);
+// inside dg_linear_wgrad_batch_begin / _end: queue part[S][n_floats] -> out into that batch's launch; false = not queued
+bool reduce_batch_try_add(const float* part, int S, long long n_floats, float* out);
+// bf16 weight pack in MFMA fragment order, mb_size 32 or 16 (gemm_bf16.hip)
+int pack_bf16(const float* w, void* packed, int rows, int cols, int mode, int mb_size, hipStream_t stream);
+
 // ---- dynamic LDS opt-in -------------------------------------------------------
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel: it has to be set
 // on every device the kernel is launched on (nn.DataParallel drives several GPUs from one process),

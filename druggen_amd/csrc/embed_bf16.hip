@@ -24,8 +24,6 @@
 
 namespace dg {
 
-void launch_splitk_reduce(const float* part, int S, int64_t n4, float* out, hipStream_t stream);
-
 namespace {
 
 constexpr int kC = 128, kH = 64, kEP = 8;

@@ -16,7 +16,6 @@
 #include "embed_sym.h"
 
 namespace dg {
-void launch_ln_finish(const float* part, int nblocks, int K, int C, float* out0, float* out1, hipStream_t stream);      // layernorm.hip
 namespace {
 
 // Pre-split layer-2 weight operands: P[((t * KS + ks) * 3 + plane) * 64 + lane] = 8 bf16 { B[16 ks + 8 (lane >> 5) + j][32 t + (lane & 31)] }_j.

@@ -31,9 +31,6 @@
 
 namespace dg {
 
-int pack_bf16(const float* w, void* packed, int rows, int cols, int mode, int mb_size, hipStream_t stream);
-void launch_splitk_reduce(const float* part, int S, int64_t n4, float* out, hipStream_t stream);
-
 namespace {
 
 constexpr int kC = 128, kH = 384;

@@ -369,8 +369,6 @@ bool aligned16(P... p) {
 
 }  // namespace
 
-bool reduce_batch_try_add(const float* part, int S, long long n_floats, float* out);      // linear_wgrad.hip
-
 // out_k[c] = sum_b part[b][k][c] in a fixed order (shared with the LayerNorm-backward epilogue of row_gemm.hip)
 void launch_ln_finish(const float* part, int nblocks, int K, int C, float* out0, float* out1, hipStream_t stream) {
     hipLaunchKernelGGL(ln_finish_kernel, dim3((C + 31) / 32, K), dim3(1024), 0, stream, part, nblocks, K, C, out0, out1);

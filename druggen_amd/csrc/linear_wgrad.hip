@@ -23,7 +23,6 @@
 #include <type_traits>
 
 namespace dg {
-void launch_ln_finish(const float* part, int nblocks, int K, int C, float* out0, float* out1, hipStream_t stream);      // layernorm.hip
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));

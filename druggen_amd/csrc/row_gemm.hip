@@ -8,13 +8,18 @@
 //   dgrad     B[k][n] = W[k][n]    (dx = dy W)              -> pack mode 1
 //   epilogue: + bias, ReLU, + residual, LayerNorm(gamma, beta) -> y (+ mean, rstd), or a LayerNorm backward
 //
-// This file: the host entry points, the weight pack (fp16 hi + lo planes in MFMA fragment order, never through LDS), the
-// 128 -> 128 kernels (row_gemm_h3_kernel, also the three-output 128 -> 384 form of the q / k / v launch) and the 384 -> 128
-// kernel over three separate [R,128] operands (row_gemm_h3_k384_kernel).  The edge-level 128 -> 384 and 384 -> 128 GEMMs
-// are row_gemm_n384.hip and row_gemm_k384.hip.  The fp32-MFMA and bf16 x 6 kernels of rounds 1 - 2 are gone.
+// This file: the host entry points (declared in row_gemm.h), the weight pack (fp16 hi + lo planes in MFMA fragment order,
+// never through LDS) and two kernels:
+//   row_gemm_h3_kernel       the four 128 -> 128 forms (direct, exchange, LayerNorm backward out / in) and the node-level
+//                            three-output q / k / v launch (dg_row_gemm_lin3);
+//   row_gemm_h3_sum3_kernel  the input gradient of those three Linears: three [R,128] operands, optional residual
+//                            (dg_row_gemm_sum3).
+// Every 128 -> 384 and 384 -> 128 launch of dg_row_gemm, ReLU bit masks included, is row_gemm_n384.hip / row_gemm_k384.hip.
+// The fp32-MFMA and bf16 x 6 kernels of rounds 1 - 2 are gone.
 #include "common.h"
 #include "f16_scale.h"
 #include "lane_reduce.h"
+#include "row_gemm.h"
 #include "row_gemm_n384.h"
 #include "row_gemm_k384.h"
 #include "traversal.h"
@@ -22,14 +27,6 @@
 #include <cstring>
 #include <type_traits>
 
-// Developer builds only (-DDG_DBG=<bits>, loaded through DG_LIB; scripts/gemm_phases.py, scripts/gemm_variants.py;
-// results in profiles/r02_gemm_*_phases.txt).  16: s_memtime phase stamps of workgroup 17 written to ep.rstd;
-// K = 384 kernel ablations: 1 = no MFMAs, 2 = raw LDS writes instead of the fp16 split, 8 = no global fetch; K = 128
-// kernels (direct epilogue): 1 = no MFMAs, 4 = no result stores, 8 = no global fetch (profiles/r04_gemm_ablation.txt).
-// The shipped library is built with DG_DBG = 0: every such block folds away.
-#ifndef DG_DBG
-#define DG_DBG 0
-#endif
 namespace dg {
 namespace {
 
@@ -38,17 +35,20 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kTR = 64;          // rows per workgroup tile
 
 struct Epilogue {
-    const float* bias;      // [N] or null
-    const unsigned* mask_bits;  // per (tile, wave, lane) bit mask written by a ReLU forward of the SAME geometry
-    unsigned* relu_bits;        // optional output of the ReLU epilogue: bit (16*m + reg) = (v > 0)
-    const float* residual;  // [R,N] or null
-    const float* gamma;     // LayerNorm (needs N == 128) or null
-    const float* beta;
-    float* mean;
-    float* rstd;
-    float* pre;             // optional [R,N]: the pre-LayerNorm sum, saved for the backward
-    float eps;
-    int relu;
+    const float* bias = nullptr;      // [N] or null
+    // Three Linears in one launch (NG = 3 kernel; q / k / v of an attention block, reference layers.py:111-113): column
+    // groups 1 / 2 go to y_alt[0] / y_alt[1] (row pitch 128, like y), their bias comes from bias_alt[0] / bias_alt[1].
+    // (y_alt sits here, where the ReLU bit-mask pointers used to be: the fields below keep their kernel-argument offsets,
+    // and hipcc groups the scalar loads of the 128 -> 128 instances as it always has)
+    float* y_alt[2] = {nullptr, nullptr};
+    const float* residual = nullptr;  // [R,N] or null
+    const float* gamma = nullptr;     // LayerNorm (needs N == 128) or null
+    const float* beta = nullptr;
+    float* mean = nullptr;
+    float* rstd = nullptr;
+    float* pre = nullptr;             // optional [R,N]: the pre-LayerNorm sum, saved for the backward
+    float eps = 0.f;
+    int relu = 0;
     // LayerNorm-BACKWARD epilogue (LNB kernels): v = a B + residual is the gradient of a LayerNorm output; the row
     // leaves as dz = rstd (v gamma - mean(v gamma) - xhat mean(v gamma xhat)), xhat = (lnb_pre - mean) rstd, with
     // `gamma`, `mean`, `rstd` above read as that LayerNorm's saved parameters / statistics.  Per half-wave partial sums
@@ -61,13 +61,7 @@ struct Epilogue {
     // to lnb_part in the layout above (half-waves of the four producer waves).
     const float* lna_pre = nullptr;
     float* lna_dz = nullptr;
-    // Three Linears in one launch (q / k / v of an attention block, reference layers.py:111-113 and their backward):
-    //   128 -> 384, S3 kernels: output slabs 4..7 / 8..11 go to y_alt[0] / y_alt[1] (row pitch 128, like y), their bias
-    //   comes from bias_alt[0] / bias_alt[1];
-    //   384 -> 128, A3 kernels: k-chunks 1 / 2 of the A operand are the [R,128] matrices a_alt[0] / a_alt[1].
-    float* y_alt[2] = {nullptr, nullptr};
     const float* bias_alt[2] = {nullptr, nullptr};
-    const float* a_alt[2] = {nullptr, nullptr};
     int reverse = 0;      // 128 -> 128 kernels without LayerNorm-backward stages: tiles in descending order (traversal.h)
 };
 
@@ -244,20 +238,20 @@ __global__ __launch_bounds__(512) void pack_weight_h3_batch_kernel(const long lo
 //   waves 0..3  consumers: wave w = 32-column slab w of the current 128-column group: 3 MFMAs per
 //               (k-step, 32-row block) on fragments read from the planes, then the epilogue.
 // One barrier per chunk separates "planes[c] written" from "planes[c] read".  K = 128: one chunk per tile.
-// NG = 3 (the three-output q / k / v launch): the three column groups of a tile run back to back on the same planes,
-// and the B fragments of a group (64 VGPRs, two halves) are double-buffered: the next group's arrive from L2 during
-// this group's MFMAs.  NG = 1: the B fragments stay resident.
-template <int NG, bool EXCH, bool LNB = false, bool LNA = false, bool S3 = false>
+// NG = 1, the four 128 -> 128 forms: direct epilogue (bias, ReLU), exchange epilogue (EXCH: + residual, LayerNorm),
+// LayerNorm backward as the epilogue (LNB) or on the way in (LNA); the B fragments stay resident.
+// NG = 3, the node-level q / k / v launch: three [R,128] outputs, one column group per Linear.  The three groups of a
+// tile run back to back on the same planes, and the B fragments of a group (64 VGPRs, two halves) are double-buffered:
+// the next group's arrive from L2 during this group's MFMAs.
+template <int NG, bool EXCH, bool LNB = false, bool LNA = false>
 __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __restrict__ a, const f16x8* __restrict__ packed,
                                                              float* __restrict__ y, int64_t R, Epilogue ep) {
     // K = 128: one chunk per tile, the row scale covers the whole contraction
     constexpr int NC = 4, NM = 8 - NC, PFN = 2048 / (64 * NM);   // consumer / producer waves, float4 per producer thread and chunk
-    constexpr int K = 128, KS = 8, N = 128 * NG;
-    constexpr int SLABS = 4 * NG;   // 32-column slabs of the whole output (bit-mask layout)
-    constexpr int NS = 1;           // slabs per consumer wave (the loops over it shape hipcc's schedule of the NG = 3 instance)
+    constexpr int K = 128, KS = 8;
     static_assert(!LNB || (EXCH && NG == 1), "LayerNorm-backward epilogue: 128 -> 128 exchange kernel");
     static_assert(!LNA || (!EXCH && !LNB && NG == 1), "LayerNorm-backward prologue: plain 128 -> 128 kernel");
-    static_assert(!S3 || (NG == 3 && !EXCH), "three outputs: the streaming-B 128 -> 384 kernel (one column group per Linear)");
+    static_assert(NG == 1 || (NG == 3 && !EXCH && !LNB && !LNA), "three outputs: direct epilogue, one column group per Linear");
     constexpr int DEPTH = LNA ? 2 : 3;      // register sets of A chunks the producers keep in flight
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     char* lds = smem_raw;                              // 2 x { planes[2][64 rows][272 B], inv_row_scale[64] }
@@ -276,7 +270,7 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
     // tiles round-robin over the workgroups, ascending or (ep.reverse, traversal.h) descending
     auto tile_at = [&](int64_t ti) {
         const int64_t t = blockIdx.x + ti * gridDim.x;
-        if constexpr (LNB || LNA || S3) return t;      // (partial sums per workgroup / node-level kernels: always ascending)
+        if constexpr (LNB || LNA || NG == 3) return t;      // (partial sums per workgroup / node-level kernels: always ascending)
         else return ep.reverse ? tiles - 1 - t : t;
     };
 
@@ -420,8 +414,7 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
             for (int i = 0; i < PFN; ++i) {
                 unsigned off = voff0 + i * (2 * NM * K * 4);   // 64 NM threads = 2 NM rows per step
                 off = off < lim ? off : lim;
-                if (DG_DBG & 8) set[i] = f4(static_cast<float>(off & 7));
-                else set[i] = ld4(reinterpret_cast<const float*>(base + off));
+                set[i] = ld4(reinterpret_cast<const float*>(base + off));
             }
         };
         auto write = [&](const float4 (&set)[PFN], int64_t chunk) {   // chunks past the end land in the idle buffer
@@ -434,12 +427,6 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
             }
             __syncthreads();
         };
-#if DG_DBG & 16
-        unsigned long long tl = __builtin_amdgcn_s_memtime(), tW = 0, tF = 0, tB = 0, t00 = tl;
-#define GSTAMP(x) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); x += t_ - tl; tl = t_; }
-#else
-#define GSTAMP(x)
-#endif
         fetch(pf[0], 0);
         fetch(pf[1], 1);
         fetch(pf[2], 2);
@@ -448,91 +435,61 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
         __syncthreads();
         for (int64_t c = 0; c < padded; c += 3) {
             // iteration c writes chunk c + 1 (the consumers are on chunk c) and refills its register set
-            write(pf[1], c + 1); GSTAMP(tW)
-            fetch(pf[1], c + 4); GSTAMP(tF)
-            end_of_iteration(c); GSTAMP(tB)
-            write(pf[2], c + 2); GSTAMP(tW)
-            fetch(pf[2], c + 5); GSTAMP(tF)
-            end_of_iteration(c + 1); GSTAMP(tB)
-            write(pf[0], c + 3); GSTAMP(tW)
-            fetch(pf[0], c + 6); GSTAMP(tF)
-            end_of_iteration(c + 2); GSTAMP(tB)
+            write(pf[1], c + 1);
+            fetch(pf[1], c + 4);
+            end_of_iteration(c);
+            write(pf[2], c + 2);
+            fetch(pf[2], c + 5);
+            end_of_iteration(c + 1);
+            write(pf[0], c + 3);
+            fetch(pf[0], c + 6);
+            end_of_iteration(c + 2);
         }
-#if DG_DBG & 16
-        if (lane == 0 && blockIdx.x == 17 && ep.rstd) {
-            unsigned long long* o = reinterpret_cast<unsigned long long*>(ep.rstd) + 8 * w;
-            o[0] = tW; o[1] = tF; o[2] = tB; o[3] = 0; o[4] = __builtin_amdgcn_s_memtime() - t00; o[5] = my_tiles;
-        }
-#endif
         return;
     }
 
     // ---------------------------------------------------------------------- consumers
-    const unsigned relu_sel = ep.relu ? 0xFFFFFFFFu : 0u;
-    // B fragments of the current unit in two halves (k-steps 0-3 and 4-7, 32 VGPRs each).  When the
-    // unit changes (K = 384 or N = 384) the halves form a ring: half 1 of this unit is requested from L2
-    // at the start of the unit, half 0 of the next unit after the first four k-steps.
-    f16x8 bset[2][NS][2][4];
-    auto slab_of = [&](int g, int) { return 4 * g + w; };      // (column group, slab of the wave)
-    auto load_b = [&](f16x8 (&bfr)[NS][2][4], int g, int h) {
+    // B fragments of the current unit in two halves (k-steps 0-3 and 4-7, 32 VGPRs each).  When the unit changes
+    // (NG = 3) the halves form a ring: half 1 of this unit is requested from L2 at the start of the unit, half 0 of
+    // the next unit after the first four k-steps.
+    f16x8 bset[2][2][4];
+    auto slab_of = [&](int g) { return 4 * g + w; };      // the wave's 32-column slab of column group g
+    auto load_b = [&](f16x8 (&bfr)[2][4], int g, int h) {
+        const f16x8* wp = packed + static_cast<size_t>(slab_of(g)) * KS * 2 * 64 + lane;
 #pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const f16x8* wp = packed + static_cast<size_t>(slab_of(g, s)) * KS * 2 * 64 + lane;
+        for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-                for (int p = 0; p < 2; ++p) bfr[s][p][ks] = wp[((4 * h + ks) * 2 + p) * 64];
-        }
+            for (int p = 0; p < 2; ++p) bfr[p][ks] = wp[((4 * h + ks) * 2 + p) * 64];
     };
-    const float* inv_cs = reinterpret_cast<const float*>(packed + static_cast<size_t>(SLABS) * KS * 2 * 64);
-    float bias_g[NG * NS], cs_g[NG * NS];   // NS > 1 only with NG == 1
+    const float* inv_cs = reinterpret_cast<const float*>(packed + static_cast<size_t>(4 * NG) * KS * 2 * 64);
+    float bias_g[NG], cs_g[NG];
 #pragma unroll
-    for (int g = 0; g < NG; ++g)
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int n = 32 * slab_of(g, s) + col;
-            if (S3) {      // slab / 4 selects the Linear, n & 127 its output channel
-                const float* bp = n < 128 ? ep.bias : ep.bias_alt[(n >> 7) - 1];
-                bias_g[g * NS + s] = bp ? bp[n & 127] : 0.f;
-            } else {
-                bias_g[g * NS + s] = ep.bias ? ep.bias[n] : 0.f;
-            }
-            cs_g[g * NS + s] = inv_cs[n];
+    for (int g = 0; g < NG; ++g) {
+        const int n = 32 * slab_of(g) + col;
+        if (NG == 3) {      // the column group selects the Linear, n & 127 its output channel
+            const float* bp = n < 128 ? ep.bias : ep.bias_alt[(n >> 7) - 1];
+            bias_g[g] = bp ? bp[n & 127] : 0.f;
+        } else {
+            bias_g[g] = ep.bias ? ep.bias[n] : 0.f;
         }
+        cs_g[g] = inv_cs[n];
+    }
     float4 res[8];   // EXCH: residual rows of the tile, requested before its MFMAs
     float4 lpre[LNB ? 4 : 1];      // LNB: rows of the saved pre-LayerNorm sum (four at a time)
     float4 dgam = f4(0.f), dbet = f4(0.f);      // LNB: this lane's four columns, summed over every row it finishes
-    f32x16 acc[NS][2];
-#if DG_DBG & 16
-    unsigned long long tl = 0, tM = 0, tE = 0, tB = 0, t00 = 0, tC = 0, tS = 0;
-#endif
-    // one unit = one (chunk, column group): MFMAs on planes[chunk & 1] with `bfr`, epilogue when the
-    // contraction is complete; `bnext` receives the B fragments of the following unit meanwhile
+    f32x16 acc[2];
+    // one unit = one (tile, column group): MFMAs on planes[chunk & 1] with the two halves of `bset`, then the epilogue;
+    // NG = 3: each half is refilled with the following unit's fragments as soon as its MFMAs are issued
     auto unit = [&](int64_t ti, int pos_g) {   // positions within the tile; values are rotated
         const int g = NG > 1 ? (pos_g + rot) % NG : 0;
         const int64_t chunk = ti;
         const int64_t tix = tile_at(ti);
         const int64_t r0 = tix * kTR;
         if (NG > 1) load_b(bset[1], g, 1);
-        // ReLU mask words of this unit's slabs, requested before the MFMA phase and unconditionally (a null mask reads a
-        // valid dummy word): a load inside the epilogue would be awaited with vmcnt(0) -- i.e. behind the stores
-        // the previous slab has just issued -- once per slab, whether or not a mask is present
-        constexpr bool BITS_IN = !EXCH && NG == 3;
-        unsigned mask_in[NS];
-        if (BITS_IN) {
 #pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const size_t bix = (static_cast<size_t>(tix) * SLABS + slab_of(g, s)) * 64 + lane;
-                const unsigned* mp = ep.mask_bits ? ep.mask_bits + bix : reinterpret_cast<const unsigned*>(packed) + lane;
-                mask_in[s] = *mp;
-            }
-        }
+        for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[s][m][i] = 0.f;
+            for (int i = 0; i < 16; ++i) acc[m][i] = 0.f;
         // rows of this wave in the exchange epilogue: w * 16 + it * 2 + half, clamped to the last row of a partial tile
         // in 32 bits: uniform 64-bit tile base + a per-lane byte offset derived HERE from lane terms that are opaque per
         // tile (as loop invariants the per-row pointers are hoisted out of the tile loop and spilled)
@@ -576,86 +533,55 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
                 load_b(bset[0], (un + rot) % NG, 0);
             }
             const f16x8(&f)[2][2] = af[ks & 1];
-            const f16x8(&bfr)[NS][2][4] = bset[ks >> 2];
+            const f16x8(&bfr)[2][4] = bset[ks >> 2];
             constexpr int TA[3] = {1, 0, 0}, TB[3] = {0, 1, 0};   // lo.hi, hi.lo, hi.hi: smallest terms first
 #pragma unroll
             for (int t = 0; t < 3; ++t)
 #pragma unroll
-                for (int s = 0; s < NS; ++s)
-#pragma unroll
-                    for (int m = 0; m < 2; ++m) {
-                        if (DG_DBG & 1) asm volatile("" ::"v"(f[m][TA[t]]), "v"(bfr[s][TB[t]][ks & 3]));
-                        else acc[s][m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f[m][TA[t]], bfr[s][TB[t]][ks & 3], acc[s][m], 0, 0, 0);
-                    }
+                for (int m = 0; m < 2; ++m)
+                    acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f[m][TA[t]], bfr[TB[t]][ks & 3], acc[m], 0, 0, 0);
         }
-        GSTAMP(tM)
-        // The ReLU mask words were requested before the MFMA phase and have long arrived, but hipcc placed the wait for
-        // mask word s at its first use -- behind the stores of slab s - 1 -- as vmcnt(0): the wave sat out an HBM write
-        // round trip per tile.  Waiting HERE (nothing is outstanding but last tile's stores, issued a whole MFMA phase
-        // ago) tells the compiler's scoreboard that every earlier load is back: the slabs' stores then stream without a
-        // wait between them (128 -> 384: 310 -> 296 us at R = 518 400, A/B in one call).
-        if (BITS_IN) wait_all_vmem_visible();
         if (!EXCH) {
-            // direct epilogue from the accumulator layout, one (slab, 32-row block) at a time
-            constexpr bool BITS = NG == 3;   // ReLU bit masks in / out: only the fc1-shaped launches use them
+            // direct epilogue from the accumulator layout, one 32-row block at a time; y and its two siblings (NG = 3:
+            // the column group selects the output) all have row pitch 128
             const bool full = r0 + kTR <= R;
+            const float bias = bias_g[g];
+            float* yb = y;
+            if constexpr (NG == 3) {
+                if (g > 0) yb = ep.y_alt[g - 1];
+            }
 #pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const int slab = slab_of(g, s);
-                const int n = 32 * slab + col;
-                const float bias = bias_g[g * NS + s];
-                const size_t bix = (static_cast<size_t>(tix) * SLABS + slab) * 64 + lane;
-                unsigned bits = 0xFFFFFFFFu, newbits = 0;
-                if (BITS) bits = ep.mask_bits ? mask_in[s] : 0xFFFFFFFFu;
+            for (int m = 0; m < 2; ++m) {
+                float out[16];
+                float4 rs[4];
+                row_scales(rs, m, cs_g[g]);
 #pragma unroll
-                for (int m = 0; m < 2; ++m) {
-                    float out[16];
-                    float4 rs[4];
-                    row_scales(rs, m, cs_g[g * NS + s]);
-#pragma unroll
-                    for (int reg = 0; reg < 16; ++reg) {
-                        float v = fmaf(acc[s][m][reg], comp(rs[reg >> 2], reg & 3), bias);
-                        if (BITS) {
-                            newbits |= (v > 0.f ? 1u : 0u) << (16 * m + reg);
-                            v = __uint_as_float((__float_as_uint(fmaxf(v, 0.f)) & relu_sel) | (__float_as_uint(v) & ~relu_sel));
-                            v = (bits >> (16 * m + reg)) & 1u ? v : 0.f;
-                        } else if (ep.relu) {
-                            v = fmaxf(v, 0.f);
-                        }
-                        out[reg] = v;
-                    }
-                    GSTAMP(tC)
-                    // Leave as whole 128-byte row segments: the 32 x 32 block goes through a wave-private 4 KiB LDS tile
-                    // (no barrier: one wave, LDS operations stay in order) and out as four 16-byte-per-lane stores, each
-                    // covering 8 rows -- instead of sixteen 4-byte-per-lane stores, which cost the consumers as much
-                    // time as their MFMAs (profiles/r02_gemm_n384_phases.txt).
-                    {
-                        float* xw = xb + w * (32 * 32);
-#pragma unroll
-                        for (int reg = 0; reg < 16; ++reg) xw[((reg & 3) + 8 * (reg >> 2) + 4 * half) * 32 + col] = out[reg];
-                        __builtin_amdgcn_wave_barrier();   // compiler-level ordering only: other lanes' writes are read below
-                        float4 rowv[4];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) rowv[i] = ld4(xw + (8 * i + (lane >> 3)) * 32 + 4 * (lane & 7));
-                        __builtin_amdgcn_wave_barrier();
-                        constexpr int LDY = S3 ? 128 : N;      // three [R,128] outputs, or one [R,N]
-                        float* yb = S3 ? (slab < 4 ? y : ep.y_alt[(slab >> 2) - 1]) : y;
-                        float* yr = yb + (r0 + 32 * m + (lane >> 3)) * LDY + 32 * (S3 ? (slab & 3) : slab) + 4 * (lane & 7);
-                        if (DG_DBG & 4) {
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(rowv[i].x), "v"(rowv[i].y), "v"(rowv[i].z), "v"(rowv[i].w));
-                        } else if (full) {
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) st4(yr + static_cast<size_t>(8 * i) * LDY, rowv[i]);
-                        } else {
-#pragma unroll
-                            for (int i = 0; i < 4; ++i)
-                                if (r0 + 32 * m + 8 * i + (lane >> 3) < R) st4(yr + static_cast<size_t>(8 * i) * LDY, rowv[i]);
-                        }
-                    }
-                    GSTAMP(tS)
+                for (int reg = 0; reg < 16; ++reg) {
+                    float v = fmaf(acc[m][reg], comp(rs[reg >> 2], reg & 3), bias);
+                    if (ep.relu) v = fmaxf(v, 0.f);
+                    out[reg] = v;
                 }
-                if (BITS && ep.relu_bits) ep.relu_bits[bix] = newbits;
+                // Leave as whole 128-byte row segments: the 32 x 32 block goes through a wave-private 4 KiB LDS tile
+                // (no barrier: one wave, LDS operations stay in order) and out as four 16-byte-per-lane stores, each
+                // covering 8 rows -- instead of sixteen 4-byte-per-lane stores, which cost the consumers as much
+                // time as their MFMAs (profiles/r02_gemm_n384_phases.txt).
+                float* xw = xb + w * (32 * 32);
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) xw[((reg & 3) + 8 * (reg >> 2) + 4 * half) * 32 + col] = out[reg];
+                __builtin_amdgcn_wave_barrier();   // compiler-level ordering only: other lanes' writes are read below
+                float4 rowv[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) rowv[i] = ld4(xw + (8 * i + (lane >> 3)) * 32 + 4 * (lane & 7));
+                __builtin_amdgcn_wave_barrier();
+                float* yr = yb + (r0 + 32 * m + (lane >> 3)) * 128 + 32 * w + 4 * (lane & 7);
+                if (full) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) st4(yr + static_cast<size_t>(8 * i) * 128, rowv[i]);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (r0 + 32 * m + 8 * i + (lane >> 3) < R) st4(yr + static_cast<size_t>(8 * i) * 128, rowv[i]);
+                }
             }
         }
         if (EXCH) {
@@ -677,7 +603,7 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
 #pragma unroll
                 for (int reg = 0; reg < 16; ++reg) {
                     const int rr = 32 * m + (reg & 3) + 8 * (reg >> 2) + 4 * half;
-                    float v = fmaf(acc[0][m][reg], comp(rs[m][reg >> 2], reg & 3), bias);
+                    float v = fmaf(acc[m][reg], comp(rs[m][reg >> 2], reg & 3), bias);
                     if (ep.relu) v = fmaxf(v, 0.f);
                     ex[rr * 128 + 32 * w + col] = v;
                 }
@@ -785,16 +711,11 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
                 else finish_rows(std::true_type{});
             }
         }
-        GSTAMP(tE)
         if (pos_g == NG - 1) __syncthreads();   // end of this chunk's iteration
-        GSTAMP(tB)
     };
     load_b(bset[0], NG > 1 ? rot : 0, 0);
     if (NG == 1) load_b(bset[1], 0, 1);
     __syncthreads();   // chunk 0 is in planes[0]
-#if DG_DBG & 16
-    tl = t00 = __builtin_amdgcn_s_memtime();
-#endif
     for (int64_t ti = 0; ti < my_tiles; ++ti) {
         if constexpr (NG == 1) {
             unit(ti, 0);
@@ -809,29 +730,22 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_kernel(const float* __rest
         st4(pp, dgam);
         st4(pp + 128, dbet);
     }
-#if DG_DBG & 16
-    if (lane == 0 && blockIdx.x == 17 && ep.rstd) {
-        unsigned long long* o = reinterpret_cast<unsigned long long*>(ep.rstd) + 8 * w;
-        o[0] = tM; o[1] = tE; o[2] = tB; o[3] = 0; o[4] = __builtin_amdgcn_s_memtime() - t00; o[5] = my_tiles;
-        o[6] = tC; o[7] = tS;
-    }
-#endif
-#undef GSTAMP
 }
 
 
 // ------------------------------------------------------------------------------------------------------
-// K = 384 -> N = 128 (fc2 forward, fc1 input gradient): the contraction is three 128-wide chunks whose B
-// fragments cannot all be resident (3 x 96 VGPRs), and re-reading 96 KiB from L2 for every 64-row unit
-// bounds the MFMA phase (every CU pulls the same bytes: ~15-19 TB/s in aggregate).  This program
+// sum3: y = a0 B0 + a1 B1 + a2 B2 (+ residual), the input gradient of the q / k / v Linears of an attention block.
+// A 384 -> 128 contraction whose three 128-wide chunks are three separate [R,128] matrices.  The B fragments of
+// the chunks cannot all be resident (3 x 96 VGPRs), and re-reading 96 KiB from L2 for every 64-row unit bounds the
+// MFMA phase (every CU pulls the same bytes: ~15-19 TB/s in aggregate).  This program
 //   * walks two tiles at a time, position major -- (t0,0) (t1,0) (t0,1) (t1,1) (t0,2) (t1,2) -- so one set
 //     of B fragments serves two units (two accumulator sets);
 //   * refills the fragments by hand: the load of a k-step's registers is issued right after their last
 //     MFMA in the second unit of a position, the first unit of the next position waits per k-step with the
 //     exact in-order count (3 (7 - ks) younger loads) -- the consumers issue no other VMEM operation;
 //   * keeps every global access in waves 4..7: A chunks HBM -> registers (three deep) -> split -> fp16
-//     planes, and the finished tile's epilogue (exchange tile in LDS -> residual / LayerNorm -> 512-byte
-//     row stores).  Their loop is one straight line per tile pair so that hipcc can count loads in flight.
+//     planes, and the finished tile's epilogue (exchange tile in LDS -> + residual -> 512-byte row stores).
+//     Their loop is one straight line per tile pair so that hipcc can count loads in flight.
 // Barriers: B(c) ends every chunk; A(c) precedes the exchange-tile write of a chunk that completes a tile.
 __device__ __forceinline__ void load_b128_async(f16x8& dst, const f16x8* p) {
     asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst) : "v"(p) : "memory");
@@ -841,9 +755,14 @@ __device__ __forceinline__ void wait_b_refill(f16x8& b0, f16x8& b1) {
     asm volatile("s_waitcnt vmcnt(%2)" : "+v"(b0), "+v"(b1) : "n"(N));
 }
 
-template <bool EXCH>
-__global__ __launch_bounds__(512, 2) void row_gemm_h3_k384_kernel(const float* __restrict__ a, const f16x8* __restrict__ packed,
-                                                                  float* __restrict__ y, int64_t R, Epilogue ep) {
+struct Sum3Operands {
+    const float* a[3];          // the three [R,128] operands: k-chunk kc of the contraction is a[kc]
+    const float* residual;      // [R,128] or null
+};
+
+template <bool RES>      // RES: in.residual is non-null
+__global__ __launch_bounds__(512, 2) void row_gemm_h3_sum3_kernel(Sum3Operands in, const f16x8* __restrict__ packed,
+                                                                  float* __restrict__ y, int64_t R) {
     constexpr int KC = 3, KS = 24;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     char* lds = smem_raw;                                          // 2 x { planes[2][64 rows][272 B], inv_row_scale[64] }
@@ -874,46 +793,34 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_k384_kernel(const float* _
         __builtin_amdgcn_s_setprio(3);
         const int pw = w - 4, pt = threadIdx.x - 256;
         float4 pf[3][8];
-        // loads of a chunk: uniform 64-bit base (tile, k chunk) + a 32-bit per-lane byte offset; rows past the end
+        // loads of a chunk: uniform 64-bit base (tile, operand) + a 32-bit per-lane byte offset; rows past the end
         // of a partial tile are clamped on the offset (row-major, so the row term dominates the comparison)
-        // the three k-chunks are three separate [R,128] matrices (row pitch 512 B), not column blocks of one [R,384]
-        constexpr int APITCH = 512;
-        const unsigned voff0 = static_cast<unsigned>(pt >> 5) * APITCH + static_cast<unsigned>(pt & 31) * 16;
+        const unsigned voff0 = static_cast<unsigned>(pt >> 5) * 512 + static_cast<unsigned>(pt & 31) * 16;
         auto fetch = [&](float4 (&set)[8], int c) {
             if (c > nchunks - 1) c = nchunks - 1;
             int ti, pos;
             chunk_map(c, ti, pos);
             const int64_t r0 = tile_row0(ti);
             const int kc = (pos + rot) % KC;
-            const char* base = reinterpret_cast<const char*>(kc == 0 ? a : ep.a_alt[kc - 1]) + r0 * 512;
+            const char* base = reinterpret_cast<const char*>(in.a[kc]) + r0 * 512;
             const int64_t last = R - 1 - r0;   // >= 0
-            const unsigned lim = last >= kTR - 1 ? 0xFFFFFFFFu : static_cast<unsigned>(last) * APITCH + static_cast<unsigned>(pt & 31) * 16;
+            const unsigned lim = last >= kTR - 1 ? 0xFFFFFFFFu : static_cast<unsigned>(last) * 512 + static_cast<unsigned>(pt & 31) * 16;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                unsigned off = voff0 + i * (8 * APITCH);
+                unsigned off = voff0 + i * (8 * 512);
                 off = off < lim ? off : lim;
-                if (DG_DBG & 8) set[i] = f4(static_cast<float>(off & 7));
-                else set[i] = ld4(reinterpret_cast<const float*>(base + off));
+                set[i] = ld4(reinterpret_cast<const float*>(base + off));
             }
         };
         auto write = [&](const float4 (&set)[8], int c) {   // chunks past the end land in the idle buffer
             // the scale of a row is per 128-wide chunk: each chunk has its own accumulation
-            if (DG_DBG & 2) {
-                char* pl = lds + (c & 1) * kH3Buf;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const int L = pt + 256 * i, r = L >> 5, c4 = L & 31;
-                    *reinterpret_cast<float4*>(pl + (i & 1) * kH3Plane + r * kH3Pitch + (c4 >> 1) * 16) = set[i];
-                }
-            } else {
-                split_write_h3<8, 256>(set, lds + (c & 1) * kH3Buf, pt);
-            }
+            split_write_h3<8, 256>(set, lds + (c & 1) * kH3Buf, pt);
         };
         float4 res[8];   // residual rows of the tile being finished: pw * 16 + it * 2 + half
         auto fetch_residual = [&](int ti) {
-            if (!EXCH || !ep.residual) return;
+            if (!RES) return;
             const int64_t r0 = tile_row0(ti);
-            const char* base = reinterpret_cast<const char*>(ep.residual) + r0 * 512;
+            const char* base = reinterpret_cast<const char*>(in.residual) + r0 * 512;
             const int64_t last = R - 1 - r0;
             const unsigned lim = last >= kTR - 1 ? 0xFFFFFFFFu : static_cast<unsigned>(last) * 512 + col * 16;
             const unsigned roff0 = static_cast<unsigned>(pw * 16 + half) * 512 + col * 16;
@@ -924,113 +831,59 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_k384_kernel(const float* _
                 res[it] = ld4(reinterpret_cast<const float*>(base + off));
             }
         };
-        auto store_tile = [&](int ti) {   // exchange tile -> residual / LayerNorm -> global rows
+        auto store_tile = [&](int ti) {   // exchange tile (+ residual) -> global rows
             const int64_t r0 = tile_row0(ti);
             const bool full = r0 + kTR <= R;
             float* yrow = y + (r0 + pw * 16 + half) * 128 + col * 4;
-            float4 gam = f4(0.f), bet = f4(0.f);
-            if (EXCH && ep.gamma) {
-                gam = ld4(ep.gamma + col * 4);
-                bet = ld4(ep.beta + col * 4);
-            }
-            // two groups of four rows (register budget); inside a group every result has its own registers and
-            // the stores follow the arithmetic
+            // two groups of four rows; inside a group every result has its own registers and the stores follow
+            // the arithmetic
 #pragma unroll
             for (int hg = 0; hg < 2; ++hg) {
-                float4 yv[4], pv[4];
-                float mu4[4], rs4[4];
+                float4 yv[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int it = 4 * hg + j, rr = pw * 16 + it * 2 + half;
-                    float4 v = ld4(ex + rr * 128 + col * 4);
-                    if (EXCH && ep.residual) v += res[it];
-                    pv[j] = v;
-                    if (EXCH && ep.gamma) {
-                        const float mu = half_sum((v.x + v.y) + (v.z + v.w)) * (1.0f / 128.0f);
-                        const float4 d = v - f4(mu);
-                        const float var = half_sum((d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w)) * (1.0f / 128.0f);
-                        const float rs = rsqrtf(var + ep.eps);
-                        v = fma4(rs * d, gam, bet);
-                        mu4[j] = mu;
-                        rs4[j] = rs;
-                    }
-                    yv[j] = v;
+                    yv[j] = ld4(ex + rr * 128 + col * 4);
+                    if (RES) yv[j] += res[it];
                 }
                 if (full) {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int it = 4 * hg + j;
-                        st4(yrow + it * 256, yv[j]);
-                        if (EXCH && ep.pre && ep.gamma) st4(ep.pre + (r0 + pw * 16 + it * 2 + half) * 128 + col * 4, pv[j]);
-                    }
+                    for (int j = 0; j < 4; ++j) st4(yrow + (4 * hg + j) * 256, yv[j]);
                 } else {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int it = 4 * hg + j, rr = pw * 16 + it * 2 + half;
-                        if (r0 + rr < R) {
-                            st4(yrow + it * 256, yv[j]);
-                            if (EXCH && ep.pre && ep.gamma) st4(ep.pre + (r0 + rr) * 128 + col * 4, pv[j]);
-                        }
-                    }
-                }
-                if (EXCH && ep.gamma && col == 0) {   // one divergent block per group for the row statistics
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int rr = pw * 16 + (4 * hg + j) * 2 + half;
-                        if (r0 + rr < R) {
-                            ep.mean[r0 + rr] = mu4[j];
-                            ep.rstd[r0 + rr] = rs4[j];
-                        }
+                        if (r0 + rr < R) st4(yrow + it * 256, yv[j]);
                     }
                 }
             }
         };
-#if DG_DBG & 16
-        unsigned long long tl = __builtin_amdgcn_s_memtime(), tW = 0, tF = 0, tB = 0, tS = 0, t00 = tl;
-#define STAMP(x) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); x += t_ - tl; tl = t_; }
-#else
-#define STAMP(x)
-#endif
-#define SYNC() { __syncthreads(); STAMP(tB) }
-#define STORE_TILE(t) { store_tile(t); STAMP(tS) }
-#define WRITE(a_, b_) { write(a_, b_); STAMP(tW) }
-#define FETCH(a_, b_) { fetch(a_, b_); STAMP(tF) }
-        FETCH(pf[0], 0);
-        FETCH(pf[1], 1);
-        FETCH(pf[2], 2);
-        WRITE(pf[0], 0);
-        FETCH(pf[0], 3);
-        SYNC();   // chunk 0 is in planes[0]
+        fetch(pf[0], 0);
+        fetch(pf[1], 1);
+        fetch(pf[2], 2);
+        write(pf[0], 0);
+        fetch(pf[0], 3);
+        __syncthreads();   // chunk 0 is in planes[0]
         int c = 0;
         for (int p = 0; p < npairs; ++p, c += 6) {
             const int t0 = 2 * p, t1 = 2 * p + 1;
-            WRITE(pf[1], c + 1); FETCH(pf[1], c + 4); SYNC();                              // (t0, 0)
-            WRITE(pf[2], c + 2); FETCH(pf[2], c + 5); SYNC();                              // (t1, 0)
-            WRITE(pf[0], c + 3); FETCH(pf[0], c + 6); SYNC();                              // (t0, 1)
-            WRITE(pf[1], c + 4); FETCH(pf[1], c + 7); fetch_residual(t0); SYNC();          // (t1, 1)
-            WRITE(pf[2], c + 5); FETCH(pf[2], c + 8); SYNC(); SYNC();             // (t0, 2): A, B
-            STORE_TILE(t0);
+            write(pf[1], c + 1); fetch(pf[1], c + 4); __syncthreads();                              // (t0, 0)
+            write(pf[2], c + 2); fetch(pf[2], c + 5); __syncthreads();                              // (t1, 0)
+            write(pf[0], c + 3); fetch(pf[0], c + 6); __syncthreads();                              // (t0, 1)
+            write(pf[1], c + 4); fetch(pf[1], c + 7); fetch_residual(t0); __syncthreads();          // (t1, 1)
+            write(pf[2], c + 5); fetch(pf[2], c + 8); __syncthreads(); __syncthreads();             // (t0, 2): A, B
+            store_tile(t0);
             fetch_residual(t1);
-            WRITE(pf[0], c + 6); FETCH(pf[0], c + 9); SYNC(); SYNC();             // (t1, 2): A, B
-            STORE_TILE(t1);
+            write(pf[0], c + 6); fetch(pf[0], c + 9); __syncthreads(); __syncthreads();             // (t1, 2): A, B
+            store_tile(t1);
         }
         if (ntl & 1) {
             const int t = ntl - 1;
-            WRITE(pf[1], c + 1); FETCH(pf[1], c + 4); SYNC();                              // (t, 0)
-            WRITE(pf[2], c + 2); FETCH(pf[2], c + 5); fetch_residual(t); SYNC();           // (t, 1)
-            WRITE(pf[0], c + 3); SYNC(); SYNC();                                  // (t, 2): A, B
-            STORE_TILE(t);
+            write(pf[1], c + 1); fetch(pf[1], c + 4); __syncthreads();                              // (t, 0)
+            write(pf[2], c + 2); fetch(pf[2], c + 5); fetch_residual(t); __syncthreads();           // (t, 1)
+            write(pf[0], c + 3); __syncthreads(); __syncthreads();                                  // (t, 2): A, B
+            store_tile(t);
         }
-#if DG_DBG & 16
-        if (lane == 0 && blockIdx.x == 17 && ep.rstd) {
-            unsigned long long* o = reinterpret_cast<unsigned long long*>(ep.rstd) + 8 * w;
-            o[0] = tW; o[1] = tF; o[2] = tB; o[3] = tS; o[4] = __builtin_amdgcn_s_memtime() - t00; o[5] = ntl;
-        }
-#endif
-#undef SYNC
-#undef STORE_TILE
-#undef WRITE
-#undef FETCH
         return;
     }
 
@@ -1044,14 +897,10 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_k384_kernel(const float* _
 #pragma unroll
             for (int p = 0; p < 2; ++p) bfr[p][ks] = b0[(ks * 2 + p) * 64];
     }
-    const float bias = ep.bias ? ep.bias[32 * w + col] : 0.f;
     const float cs = reinterpret_cast<const float*>(packed + static_cast<size_t>(4) * KS * 2 * 64)[32 * w + col];
     f32x16 accs[2][2];
     int chunk = 0;
     __syncthreads();   // chunk 0 is in planes[0]
-#if DG_DBG & 16
-    unsigned long long tl = __builtin_amdgcn_s_memtime(), tM = 0, tFo = 0, tE = 0, tB = 0, t00 = tl;
-#endif
     auto body = [&](int pos, f32x16 (&acc)[2], auto second_tag) {
         constexpr bool SECOND = decltype(second_tag)::value;
         if (pos == 0) {
@@ -1094,9 +943,7 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_k384_kernel(const float* _
             for (int t = 0; t < 3; ++t)
 #pragma unroll
                 for (int m = 0; m < 2; ++m) {
-                    if (DG_DBG & 1) {
-                        if (ks == 0 && t == 0) for (int i = 0; i < 16; ++i) part[m][i] = f[m][0][0] * (float)bfr[0][ks][i & 7];
-                    } else if (ks == 0 && t == 0) {
+                    if (ks == 0 && t == 0) {
                         const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                         part[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f[m][TA[t]], bfr[TB[t]][ks], zero, 0, 0, 0);
                     } else {
@@ -1108,7 +955,6 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_k384_kernel(const float* _
                 for (int p = 0; p < 2; ++p) load_b128_async(bfr[p][ks], bnext + (ks * 2 + p) * 64);
             }
         }
-        STAMP(tM)
         {
             const float* rsp = reinterpret_cast<const float*>(pl + kH3Rs);
 #pragma unroll
@@ -1122,23 +968,17 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_k384_kernel(const float* _
                     for (int i = 0; i < 4; ++i) acc[m][4 * q + i] = fmaf(part[m][4 * q + i], comp(r4, i), acc[m][4 * q + i]);
                 }
         }
-        STAMP(tFo)
         if (pos == KC - 1) {
             __syncthreads();   // A: the movers have finished with the previous exchange tile
-            STAMP(tB)
 #pragma unroll
             for (int m = 0; m < 2; ++m)
 #pragma unroll
                 for (int reg = 0; reg < 16; ++reg) {
                     const int rr = 32 * m + (reg & 3) + 8 * (reg >> 2) + 4 * half;
-                    float v = acc[m][reg] + bias;
-                    if (ep.relu) v = fmaxf(v, 0.f);
-                    ex[rr * 128 + 32 * w + col] = v;
+                    ex[rr * 128 + 32 * w + col] = acc[m][reg];
                 }
         }
-        STAMP(tE)
         __syncthreads();   // B
-        STAMP(tB)
         ++chunk;
     };
     for (int p = 0; p < npairs; ++p) {
@@ -1161,13 +1001,6 @@ __global__ __launch_bounds__(512, 2) void row_gemm_h3_k384_kernel(const float* _
             }
         }
     }
-#if DG_DBG & 16
-    if (lane == 0 && blockIdx.x == 17 && ep.rstd) {
-        unsigned long long* o = reinterpret_cast<unsigned long long*>(ep.rstd) + 8 * w;
-        o[0] = tM; o[1] = tFo; o[2] = tE; o[3] = tB; o[4] = __builtin_amdgcn_s_memtime() - t00; o[5] = ntl;
-    }
-#endif
-#undef STAMP
 }
 
 }  // namespace
@@ -1231,7 +1064,16 @@ int row_gemm_f32(const float* a, const float* packed, float* y, int64_t R, int K
         return fail(DG_E_ARG, "dg_row_gemm: bit masks need the 128 -> 384 shape");
     if (R == 0) return 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    Epilogue ep{bias, mask_bits, relu_bits_out, residual, gamma, beta, mean, rstd, pre_ln, eps, relu};
+    Epilogue ep;
+    ep.bias = bias;
+    ep.residual = residual;
+    ep.gamma = gamma;
+    ep.beta = beta;
+    ep.mean = mean;
+    ep.rstd = rstd;
+    ep.pre = pre_ln;
+    ep.eps = eps;
+    ep.relu = relu;
     ProfScope prof(R < edge_rows() ? DG_K_ROW_GEMM : (K == 384 ? DG_K_ROW_GEMM_E_K384 : (N == 384 ? DG_K_ROW_GEMM_E_N384 : DG_K_ROW_GEMM_E_128)), stream);
     // 128 -> 384: the producer / consumer kernel (row_gemm_n384.hip)
     if (K == 128 && N == 384) {
@@ -1261,8 +1103,6 @@ int row_gemm_f32(const float* a, const float* packed, float* y, int64_t R, int K
 }
 
 
-void launch_ln_finish(const float* part, int nblocks, int K, int C, float* out0, float* out1, hipStream_t stream);
-
 size_t row_gemm_f32_ln_bwd_workspace_bytes() { return static_cast<size_t>(256) * 8 * 256 * sizeof(float); }
 
 // dz = LayerNormBackward(a B + residual; pre, mean, rstd, gamma), dgamma, dbeta: see Epilogue::lnb_pre
@@ -1277,7 +1117,11 @@ int row_gemm_f32_ln_bwd(const float* a, const float* packed, float* dz, int64_t 
     if (workspace_bytes < row_gemm_f32_ln_bwd_workspace_bytes()) return fail(DG_E_WORKSPACE, "dg_row_gemm_ln_bwd: workspace too small");
     if (R == 0) return 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    Epilogue ep{nullptr, nullptr, nullptr, residual, gamma, nullptr, const_cast<float*>(mean), const_cast<float*>(rstd), nullptr, 0.f, 0};
+    Epilogue ep;
+    ep.residual = residual;
+    ep.gamma = gamma;
+    ep.mean = const_cast<float*>(mean);
+    ep.rstd = const_cast<float*>(rstd);
     ep.lnb_pre = pre;
     ep.lnb_part = static_cast<float*>(workspace);
     const int64_t tiles = (R + kTR - 1) / kTR;
@@ -1293,8 +1137,6 @@ int row_gemm_f32_ln_bwd(const float* a, const float* packed, float* dz, int64_t 
     return check_launch("dg_row_gemm_ln_bwd");
 }
 
-bool reduce_batch_try_add(const float* part, int S, long long n_floats, float* out);      // linear_wgrad.hip
-
 // y = dz B with dz = LayerNormBackward(dy; pre, mean, rstd, gamma) computed (and written) on the way in: see
 // Epilogue::lna_pre.  K = N = 128.
 int row_gemm_f32_ln_in(const float* dy, const float* pre, const float* mean, const float* rstd, const float* gamma,
@@ -1306,7 +1148,10 @@ int row_gemm_f32_ln_in(const float* dy, const float* pre, const float* mean, con
     if (workspace_bytes < row_gemm_f32_ln_bwd_workspace_bytes()) return fail(DG_E_WORKSPACE, "dg_row_gemm_ln_bwd_in: workspace too small");
     if (R == 0) return 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    Epilogue ep{nullptr, nullptr, nullptr, nullptr, gamma, nullptr, const_cast<float*>(mean), const_cast<float*>(rstd), nullptr, 0.f, 0};
+    Epilogue ep;
+    ep.gamma = gamma;
+    ep.mean = const_cast<float*>(mean);
+    ep.rstd = const_cast<float*>(rstd);
     ep.lna_pre = pre;
     ep.lna_dz = dz;
     ep.lnb_part = static_cast<float*>(workspace);
@@ -1335,7 +1180,8 @@ int row_gemm_f32_lin3(const float* a, const float* packed, float* y0, float* y1,
     if (R < 0) return fail(DG_E_SHAPE, "dg_row_gemm_lin3: negative row count");
     if (R == 0) return 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    Epilogue ep{b0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0};
+    Epilogue ep;
+    ep.bias = b0;
     ep.y_alt[0] = y1;
     ep.y_alt[1] = y2;
     ep.bias_alt[0] = b1;
@@ -1347,8 +1193,8 @@ int row_gemm_f32_lin3(const float* a, const float* packed, float* y0, float* y1,
     // the column-group kernel (B fragments streamed per group: these launches are node-level, one or two tiles per
     // workgroup, where residency buys nothing; the resident-B instance with three outputs spills 168 B / lane)
     constexpr int lds3 = kH3Lds + 4 * 32 * 32 * 4;
-    DG_OPT_IN_LDS((&row_gemm_h3_kernel<3, false, false, false, true>), lds3);
-    hipLaunchKernelGGL((row_gemm_h3_kernel<3, false, false, false, true>), dim3(seqs), dim3(512), lds3, stream, a,
+    DG_OPT_IN_LDS((&row_gemm_h3_kernel<3, false>), lds3);
+    hipLaunchKernelGGL((row_gemm_h3_kernel<3, false>), dim3(seqs), dim3(512), lds3, stream, a,
                        reinterpret_cast<const f16x8*>(packed), y0, R, ep);
     return check_launch("dg_row_gemm_lin3");
 }
@@ -1361,21 +1207,19 @@ int row_gemm_f32_sum3(const float* a0, const float* a1, const float* a2, const f
     if (R < 0) return fail(DG_E_SHAPE, "dg_row_gemm_sum3: negative row count");
     if (R == 0) return 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    Epilogue ep{nullptr, nullptr, nullptr, residual, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0};
-    ep.a_alt[0] = a1;
-    ep.a_alt[1] = a2;
+    const Sum3Operands in{{a0, a1, a2}, residual};
     const int64_t tiles = (R + kTR - 1) / kTR;
     const int seqs = static_cast<int>(tiles < 256 ? tiles : 256);
     ProfScope prof(R < edge_rows() ? DG_K_ROW_GEMM : DG_K_ROW_GEMM_E_K384, stream);
     constexpr int lds384 = 2 * kH3Buf + kTR * 128 * 4;
     if (residual) {
-        DG_OPT_IN_LDS((&row_gemm_h3_k384_kernel<true>), lds384);
-        hipLaunchKernelGGL((row_gemm_h3_k384_kernel<true>), dim3(seqs), dim3(512), lds384, stream, a0,
-                           reinterpret_cast<const f16x8*>(packed), y, R, ep);
+        DG_OPT_IN_LDS((&row_gemm_h3_sum3_kernel<true>), lds384);
+        hipLaunchKernelGGL((row_gemm_h3_sum3_kernel<true>), dim3(seqs), dim3(512), lds384, stream, in,
+                           reinterpret_cast<const f16x8*>(packed), y, R);
     } else {
-        DG_OPT_IN_LDS((&row_gemm_h3_k384_kernel<false>), lds384);
-        hipLaunchKernelGGL((row_gemm_h3_k384_kernel<false>), dim3(seqs), dim3(512), lds384, stream, a0,
-                           reinterpret_cast<const f16x8*>(packed), y, R, ep);
+        DG_OPT_IN_LDS((&row_gemm_h3_sum3_kernel<false>), lds384);
+        hipLaunchKernelGGL((row_gemm_h3_sum3_kernel<false>), dim3(seqs), dim3(512), lds384, stream, in,
+                           reinterpret_cast<const f16x8*>(packed), y, R);
     }
     return check_launch("dg_row_gemm_sum3");
 }

@@ -27,7 +27,7 @@ KEYS = [
     ("attn_bwd2", r"attn_bwd2_kernel"),
     ("attn_bwd", r"attn_bwd_kernel"),
     ("attn_fwd", r"attn_fwd_kernel"),
-    ("row_gemm_e_k384", r"row_gemm_k384_kernel|row_gemm_h3_k384_kernel|row_gemm_bf16_kernel(<3, 1>|ILi3ELi1E)"),
+    ("row_gemm_e_k384", r"row_gemm_k384_kernel|row_gemm_h3_k384_kernel|row_gemm_h3_sum3_kernel|row_gemm_bf16_kernel(<3, 1>|ILi3ELi1E)"),
     ("row_gemm_e_n384", r"row_gemm_n384_kernel|row_gemm_h3_kernel(<1, 1, (false|true), 6>|ILi1ELi1ELb[01]ELi6E)|row_gemm_bf16_kernel(<1, 3>|ILi1ELi3E)"),
     ("row_gemm_e128", r"row_gemm_h3_kernel(<1, 1, (false|true), 4>|ILi1ELi1ELb[01]ELi4E)|row_gemm_bf16_kernel(<1, 1>|ILi1ELi1E)"),
     ("ffn_f32", r"ffn_fused_f32_kernel"),

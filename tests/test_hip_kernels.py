@@ -163,7 +163,7 @@ def test_batched_repack_equals_single_packs(dtype):
     assert torch.equal(keep, keep0)
 
 
-@pytest.mark.parametrize("R", [1, 63, 200, 4097, 23040])
+@pytest.mark.parametrize("R", [1, 63, 200, 4097, 23040, 32800])
 def test_three_linears_per_launch_match_three_launches(R):
     """q / k / v of an attention block (reference layers.py:111-113) as ONE launch per direction: dg_row_gemm_lin3 (three
     outputs), dg_row_gemm_sum3 (dq Wq + dk Wk + dv Wv + residual), dg_linear_wgrad3 (stacked [384,128] weight gradient)
