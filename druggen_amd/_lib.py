@@ -168,6 +168,11 @@ EMBED_SMOOTH_SIGNATURES = {
     "dg_embed_sym_bwd2_smooth": (c_int, [_P] * 14 + [_P, c_size_t] + [c_int] * 7 + [_P]),
 }
 
+# add-on entry of include/druggen_hip_mol_features.h (same library): dg_mol_gather for a store with a feature plane
+MOL_FEATURES_SIGNATURES = {
+    "dg_mol_gather_features": (c_int, [_P, _P, _P, _P, c_int64, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -189,7 +194,7 @@ def load() -> ctypes.CDLL:
                 f"{LIB_PATH} not found: build it with `python -m druggen_amd.build` "
                 "(druggen_amd has no CPU / eager fallback)")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**SIGNATURES, **EMBED_KEEP_SIGNATURES, **EMBED_SMOOTH_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **EMBED_KEEP_SIGNATURES, **EMBED_SMOOTH_SIGNATURES, **MOL_FEATURES_SIGNATURES}.items():
             fn = getattr(lib, name)   # AttributeError if the .so lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = lib

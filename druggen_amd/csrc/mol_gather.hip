@@ -11,7 +11,13 @@
 // every output stream is cut into a scalar head up to the first 16-byte boundary, 16-byte stores, and a scalar tail.
 // The only data-dependent loop bound is the molecule's entry count, clamped to N N; an index outside [0, n) is clamped
 // into range and counted in `bad_index` (the one atomic of the kernel, on the error path).
+//
+// dg_mol_gather_features: the same batch from a store that carries a feature plane next to `atoms` (the reference's
+// --features node matrices, dataset.py:305-307): bits [n, N, W] u32, feature f of an atom position = bit f % 32 of word f / 32.
+// x [B, N, M] is then one-hot(atoms) in the columns below atom_dim and the bits in the columns from atom_dim up.  The index,
+// label and `a` phases are gather_bonds() for both kernels; only the x stream differs.
 #include "common.h"
+#include "../../include/druggen_hip_mol_features.h"
 
 namespace dg {
 namespace {
@@ -38,10 +44,11 @@ __device__ __forceinline__ void stream_out(T* __restrict__ dst, int total, int t
     if (tid < total - done) dst[done + tid] = value(done + tid);
 }
 
-__global__ __launch_bounds__(MG_THREADS) void mol_gather_kernel(
-    const uint8_t* __restrict__ atoms, const int64_t* __restrict__ ptr, const uint32_t* __restrict__ entries, int64_t n,
-    const int64_t* __restrict__ index, int N, int M, int E, float* __restrict__ a, int* __restrict__ labels,
-    float* __restrict__ x, int* __restrict__ bad_index) {
+// The phases both kernels share: the clamped molecule of this workgroup, its bond labels through LDS, `labels` and `a` out.
+// Returns the molecule (every lane the same value).
+__device__ __forceinline__ int64_t gather_bonds(const int64_t* __restrict__ ptr, const uint32_t* __restrict__ entries, int64_t n,
+                                                const int64_t* __restrict__ index, int N, int E, float* __restrict__ a,
+                                                int* __restrict__ labels, int* __restrict__ bad_index) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lab[];      // [N, N] bond labels, padded to 16 bytes
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x;
@@ -91,6 +98,16 @@ __global__ __launch_bounds__(MG_THREADS) void mol_gather_kernel(
                 }
             }
         });
+    return m;
+}
+
+__global__ __launch_bounds__(MG_THREADS) void mol_gather_kernel(
+    const uint8_t* __restrict__ atoms, const int64_t* __restrict__ ptr, const uint32_t* __restrict__ entries, int64_t n,
+    const int64_t* __restrict__ index, int N, int M, int E, float* __restrict__ a, int* __restrict__ labels,
+    float* __restrict__ x, int* __restrict__ bad_index) {
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    const int64_t m = gather_bonds(ptr, entries, n, index, N, E, a, labels, bad_index);
 
     // ---- x [N, M] one-hot float32 of the atom labels (N bytes of the store, read through the caches) ------------------------
     const uint8_t* __restrict__ at = atoms + m * N;
@@ -106,6 +123,47 @@ __global__ __launch_bounds__(MG_THREADS) void mol_gather_kernel(
                     cls = 0;
                     ++node;
                     l = node < N ? at[node] : 0;
+                }
+            }
+        });
+}
+
+__global__ __launch_bounds__(MG_THREADS) void mol_gather_features_kernel(
+    const uint8_t* __restrict__ atoms, const int64_t* __restrict__ ptr, const uint32_t* __restrict__ entries,
+    const uint32_t* __restrict__ bits, int64_t n, const int64_t* __restrict__ index, int N, int M, int E, int W, int A,
+    float* __restrict__ a, int* __restrict__ labels, float* __restrict__ x, int* __restrict__ bad_index) {
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    const int64_t m = gather_bonds(ptr, entries, n, index, N, E, a, labels, bad_index);
+
+    // ---- x [N, M]: columns < A one-hot of the atom label, columns >= A the feature bits (N bytes and N W words of the store,
+    // read through the caches).  node < N at every load: k < N M in value(), and value4() steps to a new row only below N.
+    const uint8_t* __restrict__ at = atoms + m * N;
+    const uint32_t* __restrict__ fb = bits + m * N * W;
+    auto element = [&](int l, const uint32_t* __restrict__ row, int col) {
+        if (col < A) return l == col ? 1.0f : 0.0f;
+        const int f = col - A;
+        return (row[f >> 5] >> (f & 31)) & 1u ? 1.0f : 0.0f;
+    };
+    stream_out<float, v4f>(
+        x + b * N * M, N * M, tid,
+        [&](int k) {
+            const int node = k / M;
+            return element(at[node], fb + node * W, k - node * M);
+        },
+        [&](int k, v4f& out) {
+            int node = k / M, col = k - node * M;
+            int l = at[node];
+            const uint32_t* __restrict__ row = fb + node * W;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                out[c] = element(l, row, col);
+                if (++col == M) {
+                    col = 0;
+                    if (++node < N) {
+                        l = at[node];
+                        row += W;
+                    }
                 }
             }
         });
@@ -138,4 +196,32 @@ extern "C" int dg_mol_gather(const uint8_t* atoms, const int64_t* ptr, const uin
     hipLaunchKernelGGL(mol_gather_kernel, dim3(static_cast<unsigned>(B)), dim3(MG_THREADS), lds, stream, atoms, ptr, entries, n,
                        index, N, M, E, a, labels, x, bad_index);
     return check_launch("dg_mol_gather");
+}
+
+extern "C" int dg_mol_gather_features(const uint8_t* atoms, const int64_t* ptr, const uint32_t* entries, const uint32_t* bits,
+                                      int64_t n, const int64_t* index, int B, int N, int M, int E, int W, int atom_dim,
+                                      float* a, int* labels, float* x, int* bad_index, dg_stream_t stream_) {
+    if (B < 0 || N < 1 || N > 256 || M < 1 || M > 255 || E < 1 || E > 16 || n < 0)
+        return fail(DG_E_SHAPE, "dg_mol_gather_features: need B >= 0, 1 <= N <= 256, 1 <= M <= 255, 1 <= E <= 16, n >= 0 (B=%d N=%d M=%d E=%d n=%lld)",
+                    B, N, M, E, static_cast<long long>(n));
+    if (atom_dim < 1 || atom_dim > M || W != (M - atom_dim + 31) / 32)
+        return fail(DG_E_SHAPE, "dg_mol_gather_features: need 1 <= atom_dim <= M and W == ceil((M - atom_dim) / 32) (M=%d atom_dim=%d W=%d)",
+                    M, atom_dim, W);
+    if (B == 0) return 0;
+    if (!atoms || !ptr || !entries || (!bits && W > 0) || !index || !a || !labels || !x || !bad_index)
+        return fail(DG_E_ARG, "dg_mol_gather_features: null pointer");
+    if (n < 1) return fail(DG_E_SHAPE, "dg_mol_gather_features: a batch of B=%d molecules needs a store with n >= 1", B);
+    if ((reinterpret_cast<uintptr_t>(a) & 3) || (reinterpret_cast<uintptr_t>(labels) & 3) || (reinterpret_cast<uintptr_t>(x) & 3) ||
+        (reinterpret_cast<uintptr_t>(entries) & 3) || (reinterpret_cast<uintptr_t>(bits) & 3) ||
+        (reinterpret_cast<uintptr_t>(bad_index) & 3) || (reinterpret_cast<uintptr_t>(ptr) & 7) ||
+        (reinterpret_cast<uintptr_t>(index) & 7))
+        return fail(DG_E_ARG, "dg_mol_gather_features: misaligned pointer (a, labels, x, entries, bits, bad_index: 4 bytes; ptr, index: 8)");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const hipError_t err = hipMemsetAsync(bad_index, 0, sizeof(int), stream);
+    if (err != hipSuccess) return fail(static_cast<int>(err), "dg_mol_gather_features: %s", hipGetErrorString(err));
+    const int lds = (N * N + 15) & ~15;
+    DG_OPT_IN_LDS(&mol_gather_features_kernel, 256 * 256);
+    hipLaunchKernelGGL(mol_gather_features_kernel, dim3(static_cast<unsigned>(B)), dim3(MG_THREADS), lds, stream, atoms, ptr, entries,
+                       bits, n, index, N, M, E, W, atom_dim, a, labels, x, bad_index);
+    return check_launch("dg_mol_gather_features");
 }

@@ -65,7 +65,7 @@ class _TrainingState:
 class ResidentTrainer:
     """``ResidentTrainer(stepper, molecules, drugs=None, *, batch_size, submodel="DrugGEN", graph=True, seed=0, eps=None,
     log_every=None)`` -- ``molecules`` / ``drugs``: ``ResidentMolecules`` on the stepper's device with the same ``(N, m_dim,
-    b_dim)``.  ``submodel="DrugGEN"`` feeds the discriminator drug batches, ``"NoTarget"`` the molecule batch (one gather
+    b_dim, atom_dim)``.  ``submodel="DrugGEN"`` feeds the discriminator drug batches, ``"NoTarget"`` the molecule batch (one gather
     serves both sides, ``train.py:340-345``).
 
     ``batch_size`` is the GLOBAL batch: under a process group (``stepper.group``) every rank holds the whole set, draws the
@@ -95,9 +95,8 @@ class ResidentTrainer:
         self.log_every = None if log_every is None else int(log_every)
         self.device = molecules.device
         for store in self.stores[1:]:
-            if (store.vertexes, store.m_dim, store.b_dim) != (molecules.vertexes, molecules.m_dim, molecules.b_dim) \
-                    or store.device != self.device:
-                raise ValueError("ResidentTrainer: molecules and drugs must share N, m_dim, b_dim and the device")
+            if any(getattr(store, k) != getattr(molecules, k) for k in ("vertexes", "m_dim", "b_dim", "atom_dim", "device")):
+                raise ValueError("ResidentTrainer: molecules and drugs must share N, m_dim, b_dim, atom_dim and the device")
         group = stepper.group
         on = dist.is_available() and dist.is_initialized()
         self.world, self.rank = (dist.get_world_size(group), dist.get_rank(group)) if on else (1, 0)

@@ -16,7 +16,16 @@ The result is bit-identical to ``load_molecules``', ``a_tensor`` carries its int
 
 Store layout (also the C ABI, include/druggen_hip.h): ``atoms`` uint8 ``[n, N]`` (PAD = 0), ``ptr`` int64 ``[n + 1]``,
 ``entries`` one word per non-zero of a molecule's dense ``[N, N]`` bond-label matrix, ``row | col << 8 | label << 16``.
-Node matrices must be one-hot: the reference's ``--features`` matrices are not and are out of scope.
+
+Node matrices are one-hot by default.  The reference's ``--features`` matrices (``dataset.py:305-307``: the one-hot atom type
+followed by 54 boolean descriptors) are taken with ``atom_dim=``: the first ``atom_dim`` columns of ``x`` must be one-hot and
+are the ``atoms`` byte, the other ``F = m_dim - atom_dim`` columns must be exactly 0 or 1 and are kept as a bit plane,
+``bits`` int32 ``[n, N, ceil(F / 32)]`` (feature ``f`` = bit ``f % 32`` of word ``f // 32``, the packing of DESIGN 3.20):
+
+    store = ResidentMolecules.from_graphs(graphs, atom_dim=13)     # x [N, 13 + 54]: 9 bytes per atom position
+    real_graphs, a_tensor, x_tensor = store.batch(idx)             # x_tensor [B, N, 67], as load_molecules returns it
+
+Such a store launches ``dg_mol_gather_features`` (include/druggen_hip_mol_features.h); everything else is the same.
 
 GPU only, no CPU fallback (``pack`` and ``split_batch`` are host-side numpy)."""
 from __future__ import annotations
@@ -75,10 +84,15 @@ def epoch_batches(order, batch_size: int, drop_last: bool = True):
 
 class ResidentMolecules:
     """``atoms`` uint8 ``[n, vertexes]``, ``ptr`` int64 ``[n + 1]``, ``entries`` int32 (the bit patterns of the uint32 words)
-    on one GPU; ``n`` molecules of ``vertexes`` atom positions, ``m_dim`` atom classes, ``b_dim`` bond classes."""
+    on one GPU; ``n`` molecules of ``vertexes`` atom positions, ``m_dim`` node columns, ``b_dim`` bond classes.  With a feature
+    plane: ``bits`` int32 ``[n, vertexes, ceil((m_dim - atom_dim) / 32)]`` (bit patterns again) and ``atom_dim``, the width of
+    the one-hot part of a node row; without one ``atom_dim == m_dim``."""
 
-    def __init__(self, atoms, ptr, entries, m_dim: int, b_dim: int):
-        for t, dtype, name in ((atoms, torch.uint8, "atoms"), (ptr, torch.int64, "ptr"), (entries, torch.int32, "entries")):
+    def __init__(self, atoms, ptr, entries, m_dim: int, b_dim: int, bits=None, atom_dim=None):
+        arrays = [(atoms, torch.uint8, "atoms"), (ptr, torch.int64, "ptr"), (entries, torch.int32, "entries")]
+        if bits is not None:
+            arrays.append((bits, torch.int32, "bits"))
+        for t, dtype, name in arrays:
             if not torch.is_tensor(t) or not t.is_cuda:
                 raise RuntimeError(f"druggen_amd.resident keeps the molecule set on the GPU (no CPU fallback); {name} is not a GPU tensor")
             if t.dtype != dtype or not t.is_contiguous() or t.device != atoms.device:
@@ -89,6 +103,16 @@ class ResidentMolecules:
         self.n, self.vertexes = int(atoms.shape[0]), int(atoms.shape[1])
         self.m_dim, self.b_dim = int(m_dim), int(b_dim)
         _check_limits(self.vertexes, self.m_dim, self.b_dim)
+        self.bits, self.atom_dim = bits, self.m_dim if atom_dim is None else int(atom_dim)
+        if bits is None:
+            if self.atom_dim != self.m_dim:
+                raise ValueError(f"ResidentMolecules: atom_dim = {self.atom_dim} of m_dim = {self.m_dim} columns needs the feature plane (bits=)")
+        else:
+            if atom_dim is None or not 1 <= self.atom_dim < self.m_dim:
+                raise ValueError(f"ResidentMolecules: a feature plane needs 1 <= atom_dim < m_dim = {self.m_dim}, got atom_dim = {atom_dim}")
+            want = (self.n, self.vertexes, _feature_words(self.m_dim - self.atom_dim))
+            if tuple(bits.shape) != want:
+                raise ValueError(f"ResidentMolecules: bits [n, N, ceil((m_dim - atom_dim) / 32)] = {want}, got {tuple(bits.shape)}")
         self.device = atoms.device
         self._captured_bad = torch.zeros(1, dtype=torch.int32, device=self.device)     # counter of calls captured in a graph
         self._captured = False
@@ -106,6 +130,17 @@ class ResidentMolecules:
         per row, a summed label outside ``[0, b_dim)``, a node id outside ``[0, N)``, graphs of different ``N``, and for
         ``N > 256``, ``b_dim > 16`` or ``m_dim > 255``."""
         return _pack(graphs, m_dim, b_dim)[:3]
+
+    @staticmethod
+    def pack_features(graphs, atom_dim, m_dim=None, b_dim=None):
+        """``pack`` for node matrices ``x [N, m_dim]`` that are a one-hot atom type in the first ``atom_dim`` columns followed
+        by ``F = m_dim - atom_dim`` feature columns of exactly 0 or 1 (the reference's ``--features``): numpy ``(atoms, ptr,
+        entries, bits)``, the first three as ``pack`` gives them for the graphs cut to their first ``atom_dim`` columns, and
+        ``bits`` uint32 ``[n, N, ceil(F / 32)]`` with feature ``f`` of an atom position in bit ``f % 32`` of word ``f // 32``
+        (unused high bits zero).  ``ValueError`` (naming the molecule) for a prefix that is not one-hot per row, a feature
+        value other than 0 or 1, ``atom_dim`` outside ``[1, m_dim]``, a graph of another width, and all of ``pack``'s."""
+        atoms, ptr, entries, _, _, bits = _pack(graphs, m_dim, b_dim, atom_dim=atom_dim)
+        return atoms, ptr, entries, bits
 
     @staticmethod
     def split_batch(data, batch_size: int):
@@ -134,40 +169,47 @@ class ResidentMolecules:
 
     # ---- upload ------------------------------------------------------------------------------------------------------
     @classmethod
-    def from_arrays(cls, atoms, ptr, entries, m_dim: int, b_dim: int, device=None):
-        """Upload the three arrays of ``pack`` (once)."""
+    def from_arrays(cls, atoms, ptr, entries, m_dim: int, b_dim: int, device=None, bits=None, atom_dim=None):
+        """Upload the three arrays of ``pack`` (once), or the four of ``pack_features`` with its ``atom_dim``; a plane without
+        a column (``atom_dim == m_dim``) is not kept."""
         device = torch.device("cuda" if device is None else device)
         if device.type != "cuda":
             raise RuntimeError(f"druggen_amd.resident keeps the molecule set on the GPU (no CPU fallback); got device {device}")
         entries = np.ascontiguousarray(entries, dtype=np.uint32)
         if entries.size == 0:
             entries = np.zeros(1, np.uint32)      # (a molecule set without a single bond: keep the pointer non-null)
+        if bits is not None:
+            bits = np.ascontiguousarray(bits, dtype=np.uint32)
+            if bits.ndim == 3 and bits.shape[2] == 0:      # F = 0: today's store
+                bits = None
+            else:
+                bits = torch.from_numpy(bits.view(np.int32)).to(device)
         return cls(torch.from_numpy(np.ascontiguousarray(atoms, dtype=np.uint8)).to(device),
                    torch.from_numpy(np.ascontiguousarray(ptr, dtype=np.int64)).to(device),
-                   torch.from_numpy(entries.view(np.int32)).to(device), m_dim, b_dim)
+                   torch.from_numpy(entries.view(np.int32)).to(device), m_dim, b_dim, bits, atom_dim)
 
     @classmethod
-    def from_graphs(cls, graphs, device=None, m_dim=None, b_dim=None):
-        """``pack`` + one upload.  ``m_dim`` / ``b_dim``: see ``pack``."""
+    def from_graphs(cls, graphs, device=None, m_dim=None, b_dim=None, atom_dim=None):
+        """``pack`` + one upload.  ``m_dim`` / ``b_dim``: see ``pack``.  ``atom_dim``: ``pack_features`` instead."""
         device = torch.device("cuda" if device is None else device)
         if device.type != "cuda":
             raise RuntimeError(f"druggen_amd.resident keeps the molecule set on the GPU (no CPU fallback); got device {device}")
-        atoms, ptr, entries, m_dim, b_dim = _pack(graphs, m_dim, b_dim)
-        return cls.from_arrays(atoms, ptr, entries, m_dim, b_dim, device)
+        atoms, ptr, entries, m_dim, b_dim, bits = _pack(graphs, m_dim, b_dim, atom_dim=atom_dim)
+        return cls.from_arrays(atoms, ptr, entries, m_dim, b_dim, device, bits=bits, atom_dim=atom_dim)
 
     @classmethod
-    def from_batch(cls, data, batch_size: int, device=None, m_dim=None, b_dim=None):
+    def from_batch(cls, data, batch_size: int, device=None, m_dim=None, b_dim=None, atom_dim=None):
         """A whole-dataset PyG-style batch (``x``, ``edge_index``, ``edge_attr``, ``batch``) split by ``split_batch``."""
         if device is None and torch.is_tensor(data.x) and data.x.is_cuda:
             device = data.x.device
-        return cls.from_graphs(cls.split_batch(data, batch_size), device=device, m_dim=m_dim, b_dim=b_dim)
+        return cls.from_graphs(cls.split_batch(data, batch_size), device=device, m_dim=m_dim, b_dim=b_dim, atom_dim=atom_dim)
 
     def __len__(self):
         return self.n
 
     def nbytes(self) -> int:
         """Device bytes of the store."""
-        return sum(t.numel() * t.element_size() for t in (self.atoms, self.ptr, self.entries))
+        return sum(t.numel() * t.element_size() for t in (self.atoms, self.ptr, self.entries, self.bits) if t is not None)
 
     # ---- batches -----------------------------------------------------------------------------------------------------
     def epoch(self, batch_size: int, *, shuffle: bool = True, drop_last: bool = True, generator=None):
@@ -230,8 +272,13 @@ class ResidentMolecules:
             if not capturing:
                 self.raise_bad_indices()      # counters of earlier calls whose host copies are complete by now
             bad = self._captured_bad if capturing else torch.empty(1, dtype=torch.int32, device=self.device)
-            _lib.launch("dg_mol_gather", a, self.atoms.data_ptr(), self.ptr.data_ptr(), self.entries.data_ptr(), self.n,
-                        index.data_ptr(), B, N, M, E, a.data_ptr(), labels.data_ptr(), x.data_ptr(), bad.data_ptr())
+            if self.bits is None:
+                _lib.launch("dg_mol_gather", a, self.atoms.data_ptr(), self.ptr.data_ptr(), self.entries.data_ptr(), self.n,
+                            index.data_ptr(), B, N, M, E, a.data_ptr(), labels.data_ptr(), x.data_ptr(), bad.data_ptr())
+            else:
+                _lib.launch("dg_mol_gather_features", a, self.atoms.data_ptr(), self.ptr.data_ptr(), self.entries.data_ptr(),
+                            self.bits.data_ptr(), self.n, index.data_ptr(), B, N, M, E, int(self.bits.shape[2]), self.atom_dim,
+                            a.data_ptr(), labels.data_ptr(), x.data_ptr(), bad.data_ptr())
             if capturing:
                 self._captured = True
             else:
@@ -288,13 +335,18 @@ class ResidentMolecules:
                                f"(they were clamped into range on the device)")
 
 
-def _pack(graphs, m_dim, b_dim):
-    """``ResidentMolecules.pack`` plus the ``m_dim`` and ``b_dim`` it settled on."""
+def _feature_words(F):
+    return (F + 31) // 32
+
+
+def _pack(graphs, m_dim, b_dim, atom_dim=None):
+    """``ResidentMolecules.pack`` plus the ``m_dim`` and ``b_dim`` it settled on and, with ``atom_dim``, the feature plane of
+    ``pack_features`` (else ``None``)."""
     graphs = list(graphs)
     if not graphs:
         raise ValueError("ResidentMolecules.pack: no molecules")
     N = None
-    atoms, counts, words = [], [], []
+    atoms, counts, words, planes = [], [], [], []
     top = 0
     for i, g in enumerate(graphs):
         x = _host_array(g.x, "x", i)
@@ -304,13 +356,27 @@ def _pack(graphs, m_dim, b_dim):
             N = int(x.shape[0])
             m_dim = int(x.shape[1] if m_dim is None else m_dim)
             _check_limits(N, m_dim, 1 if b_dim is None else int(b_dim), who="molecule 0: ")
+            if atom_dim is not None and not 1 <= int(atom_dim) <= m_dim:
+                raise ValueError(f"molecule 0: atom_dim = {atom_dim} outside [1, m_dim = {m_dim}]")
+            A = m_dim if atom_dim is None else int(atom_dim)
         if x.shape[0] != N:
             raise ValueError(f"molecule {i}: {x.shape[0]} atom positions, molecule 0 has {N} (every graph is padded to the same N)")
         if x.shape[1] != m_dim:
             raise ValueError(f"molecule {i}: x has {x.shape[1]} columns, m_dim is {m_dim}")
-        if not (((x == 0) | (x == 1)).all() and (x.sum(1) == 1).all()):
-            raise ValueError(f"molecule {i}: x is not one-hot per row (the reference's --features node matrices are out "
-                             "of scope: ResidentMolecules stores one atom label per position)")
+        if atom_dim is None:
+            if not (((x == 0) | (x == 1)).all() and (x.sum(1) == 1).all()):
+                raise ValueError(f"molecule {i}: x is not one-hot per row (the reference's --features node matrices, a "
+                                 "one-hot atom type followed by 0 / 1 columns, are taken with atom_dim=: pack_features)")
+        else:
+            x, feats = x[:, :A], x[:, A:]
+            if not (((x == 0) | (x == 1)).all() and (x.sum(1) == 1).all()):
+                raise ValueError(f"molecule {i}: the first atom_dim = {A} columns of x are not one-hot per row")
+            if not ((feats == 0) | (feats == 1)).all():
+                raise ValueError(f"molecule {i}: a feature column of x (from column atom_dim = {A} up) holds a value other "
+                                 "than 0 or 1")
+            octets = np.zeros((N, 4 * _feature_words(m_dim - A)), dtype=np.uint8)      # bit f % 8 of octet f // 8, little end first
+            octets[:, :(m_dim - A + 7) // 8] = np.packbits(feats != 0, axis=1, bitorder="little")
+            planes.append(octets.view("<u4").astype(np.uint32))
         atoms.append(x.argmax(1).astype(np.uint8))
         ei = _integers(g.edge_index, "edge_index", i)
         attr = _integers(g.edge_attr, "edge_attr", i).reshape(-1)
@@ -332,7 +398,8 @@ def _pack(graphs, m_dim, b_dim):
         counts.append(row.size)
     ptr = np.zeros(len(graphs) + 1, dtype=np.int64)
     np.cumsum(counts, out=ptr[1:])
-    return np.stack(atoms), ptr, np.concatenate(words), m_dim, (top + 1 if b_dim is None else int(b_dim))
+    return (np.stack(atoms), ptr, np.concatenate(words), m_dim, (top + 1 if b_dim is None else int(b_dim)),
+            None if atom_dim is None else np.stack(planes))
 
 
 def _check_limits(N, m_dim, b_dim, who=""):
