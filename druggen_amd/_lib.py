@@ -173,6 +173,18 @@ MOL_FEATURES_SIGNATURES = {
     "dg_mol_gather_features": (c_int, [_P, _P, _P, _P, c_int64, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
 }
 
+# add-on entries of include/druggen_hip_node_wide.h (same library): node embedding and node readout wider than 16 columns
+NODE_WIDE_SIGNATURES = {
+    "dg_embed_node_wide_chain": (c_int, [_P] * 9 + [c_int64, c_int, c_int, _P]),
+    "dg_embed_node_wide_bwd": (c_int, [_P] * 8 + [c_int64, c_int, c_int, _P]),
+    "dg_embed_node_wide_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "dg_embed_node_wide_wgrad": (c_int, [_P] * 5 + [c_size_t, c_int64, c_int, _P]),
+    "dg_wide_linear_fwd": (c_int, [_P] * 4 + [c_int64, c_int, c_int, c_int, _P]),
+    "dg_wide_linear_dgrad": (c_int, [_P] * 3 + [c_int64, c_int, c_int, c_int, _P]),
+    "dg_wide_linear_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "dg_wide_linear_wgrad": (c_int, [_P] * 5 + [c_size_t, c_int64, c_int, c_int, c_int, _P]),
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -194,7 +206,8 @@ def load() -> ctypes.CDLL:
                 f"{LIB_PATH} not found: build it with `python -m druggen_amd.build` "
                 "(druggen_amd has no CPU / eager fallback)")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**SIGNATURES, **EMBED_KEEP_SIGNATURES, **EMBED_SMOOTH_SIGNATURES, **MOL_FEATURES_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **EMBED_KEEP_SIGNATURES, **EMBED_SMOOTH_SIGNATURES, **MOL_FEATURES_SIGNATURES,
+                                  **NODE_WIDE_SIGNATURES}.items():
             fn = getattr(lib, name)   # AttributeError if the .so lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = lib

@@ -11,11 +11,18 @@ from ._runtime import _account, _c, in_second_order_forward, _inputs_only, _scra
 from .dense import _double_backward_fallback, linear, _wgrad
 
 
+def _readout_entries(N):
+    """(prefix of the _fwd / _dgrad / _wgrad entries, their workspace query) of a readout with N classes."""
+    if N <= 16:
+        return "dg_skinny_linear", "dg_linear_wgrad_workspace_bytes"
+    return "dg_wide_linear", "dg_wide_linear_wgrad_workspace_bytes"      # readout_n of a --features model (N = m_dim)
+
+
 class _Readout(Function):
-    """nn.Linear(128 -> N <= 16) over edge / node rows with float32 logits whatever the activation dtype (reference
-    models.py:67-68,100-101: readout_e / readout_n): one streaming kernel per direction (dg_skinny_linear_fwd / _dgrad,
-    dg_skinny_linear_wgrad) instead of `x.float()` + a library GEMM.  First order; a graph that is differentiated again
-    goes through the composite."""
+    """nn.Linear(128 -> N <= 255) over edge / node rows with float32 logits whatever the activation dtype (reference
+    models.py:67-68,100-101: readout_e / readout_n): one streaming kernel per direction (N <= 16: dg_skinny_linear_fwd /
+    _dgrad / _wgrad; wider: dg_wide_linear_*) instead of `x.float()` + a library GEMM.  First order; a graph that is
+    differentiated again goes through the composite."""
 
     @staticmethod
     def forward(ctx, x, w, b):
@@ -23,7 +30,7 @@ class _Readout(Function):
         x2 = _c(x).reshape(-1, K)
         R = x2.shape[0]
         y = torch.empty(R, N, dtype=torch.float32, device=x.device)
-        _lib.launch("dg_skinny_linear_fwd", x2, _lib.ptr(x2), _lib.fptr(_c(w)), _lib.fptr(None if b is None else _c(b)),
+        _lib.launch(_readout_entries(N)[0] + "_fwd", x2, _lib.ptr(x2), _lib.fptr(_c(w)), _lib.fptr(None if b is None else _c(b)),
                     _lib.ptr(y), R, N, K, _lib.dt(x2))
         _account("readout", x2.element_size() * R * K + 4 * R * N)
         ctx.save_for_backward(x, w, b)
@@ -36,20 +43,20 @@ class _Readout(Function):
             return _double_backward_fallback(lambda x_, w_, b_: torch.nn.functional.linear(x_.float(), w_, b_),
                                              (x, w, b), dy)
         N, K = w.shape
-        lib = _lib.load()
+        entry, ws_query = _readout_entries(N)
         dy2 = _c(dy.float()).reshape(-1, N)
         x2 = _c(x).reshape(-1, K)
         R = x2.shape[0]
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x2)
-            _lib.launch("dg_skinny_linear_dgrad", x2, _lib.ptr(dy2), _lib.fptr(_c(w)), _lib.ptr(dx), R, N, K, _lib.dt(x2))
+            _lib.launch(entry + "_dgrad", x2, _lib.ptr(dy2), _lib.fptr(_c(w)), _lib.ptr(dx), R, N, K, _lib.dt(x2))
             _account("readout", x2.element_size() * R * K + 4 * R * N)
         if ctx.needs_input_grad[1] and not _inputs_only():
             dw = torch.empty_like(w)
             db = torch.empty(N, dtype=torch.float32, device=x.device) if b is not None else None
-            ws = _scratch(x2, int(lib.dg_linear_wgrad_workspace_bytes(R, N, K)), "wgrad")
-            _lib.launch("dg_skinny_linear_wgrad", x2, _lib.ptr(dy2), _lib.ptr(x2), _lib.ptr(dw), _lib.ptr(db), ws.data_ptr(),
+            ws = _scratch(x2, int(getattr(_lib.load(), ws_query)(R, N, K)), "wgrad")
+            _lib.launch(entry + "_wgrad", x2, _lib.ptr(dy2), _lib.ptr(x2), _lib.ptr(dw), _lib.ptr(db), ws.data_ptr(),
                         ws.numel(), R, N, K, _lib.dt(x2))
             _account("linear_wgrad", x2.element_size() * R * K + 4 * R * N)
         return (None if dx is None else dx.view(x.shape)), dw, db
@@ -69,10 +76,31 @@ def _composite_head_tail(z1, w2, b2, w3, b3, w4, b4, act):
     return lin(f(lin(f(lin(f(z1), w2, b2)), w3, b3)), w4, b4)
 
 
+def _node_entry(E, which):
+    """dg_embed_node_chain / _bwd for E <= 16 (the launches of a model without --features, unchanged), the wide entries above."""
+    return ("dg_embed_node_" if E <= 16 else "dg_embed_node_wide_") + which
+
+
+def _node_wgrad1(g1, z2, want_bias):
+    """Weight gradient of the chain's first Linear, dW1 [64,E] = g1^T z2 (+ db1): E <= 16 as before (``_wgrad``'s swapped
+    skinny kernel), wider on dg_embed_node_wide_wgrad."""
+    R, E = z2.shape
+    if E <= 16:
+        return _wgrad(g1, z2, want_bias)
+    dw = torch.empty(64, E, dtype=torch.float32, device=g1.device)
+    db = torch.empty(64, dtype=torch.float32, device=g1.device) if want_bias else None
+    ws = _scratch(g1, int(_lib.load().dg_embed_node_wide_wgrad_workspace_bytes(R, E)), "wgrad")
+    _lib.launch("dg_embed_node_wide_wgrad", g1, _lib.ptr(g1), _lib.ptr(z2), _lib.ptr(dw), _lib.ptr(db), ws.data_ptr(), ws.numel(),
+                R, E)
+    _account("linear_wgrad", 4 * R * (64 + E), 2 * R * 64 * E)
+    return dw, db
+
+
 class _NodeEmbed(Function):
     """Linear(E, 64) - act - Linear(64, 128) - act over the node rows (reference models.py:52-56, 154-158) as ONE launch
-    (dg_embed_node_chain); backward: one launch for g2 / g1 / dz (dg_embed_node_bwd) + the two weight gradients on
-    dg_linear_wgrad; differentiable again (``_NodeEmbedBwd``: the penalty's second order is the chain kernel with the
+    (dg_embed_node_chain, E > 16: dg_embed_node_wide_chain); backward: one launch for g2 / g1 / dz (dg_embed_node_bwd /
+    dg_embed_node_wide_bwd) + the two weight gradients (dg_linear_wgrad; E > 16: the first Linear's on
+    dg_embed_node_wide_wgrad); differentiable again (``_NodeEmbedBwd``: the penalty's second order is the chain kernel with the
     activation pattern as a mask; sigmoid / tanh, act'' != 0: the composite graph)."""
 
     @staticmethod
@@ -82,7 +110,7 @@ class _NodeEmbed(Function):
         R = z2.shape[0]
         a1 = torch.empty(R, 64, dtype=torch.float32, device=z.device)
         a2 = torch.empty(R, 128, dtype=torch.float32, device=z.device)
-        _lib.launch("dg_embed_node_chain", z2, _lib.ptr(z2), None, None, _lib.fptr(_c(w1)), _lib.fptr(_c(b1)),
+        _lib.launch(_node_entry(E, "chain"), z2, _lib.ptr(z2), None, None, _lib.fptr(_c(w1)), _lib.fptr(_c(b1)),
                     _lib.fptr(_c(w2)), _lib.fptr(_c(b2)), _lib.ptr(a1), _lib.ptr(a2), R, E, act)
         ctx.save_for_backward(z2, a1, a2, w1, w2, *((z, b1, b2) if act in _SMOOTH_ACT_FNS else ()))
         ctx.act, ctx.zshape = act, z.shape
@@ -110,12 +138,12 @@ class _NodeEmbedBwd(Function):
         g2 = torch.empty(R, 128, dtype=torch.float32, device=dev)
         g1 = torch.empty(R, 64, dtype=torch.float32, device=dev)
         dz = torch.empty(R, E, dtype=torch.float32, device=dev) if need_z else None
-        _lib.launch("dg_embed_node_bwd", z2, _lib.ptr(g), _lib.ptr(a1), _lib.ptr(a2), _lib.fptr(_c(w1)), _lib.fptr(_c(w2)),
+        _lib.launch(_node_entry(E, "bwd"), z2, _lib.ptr(g), _lib.ptr(a1), _lib.ptr(a2), _lib.fptr(_c(w1)), _lib.fptr(_c(w2)),
                     _lib.ptr(g2), _lib.ptr(g1), _lib.ptr(dz), R, E, act)
         dw1 = db1 = dw2 = db2 = None
         if need_w:
             dw2, db2 = _wgrad(g2, a1, True)
-            dw1, db1 = _wgrad(g1, z2, True)
+            dw1, db1 = _node_wgrad1(g1, z2, True)
         ctx.save_for_backward(z2, a1, a2, w1, w2, g1, g2)
         ctx.act, ctx.gshape = act, gshape
         ctx.set_materialize_grads(False)
@@ -134,11 +162,11 @@ class _NodeEmbedBwd(Function):
         dev = z2.device
         u1 = torch.empty(R, 64, dtype=torch.float32, device=dev)
         u2 = torch.empty(R, 128, dtype=torch.float32, device=dev)
-        _lib.launch("dg_embed_node_chain", z2, _lib.ptr(t), _lib.ptr(a1), _lib.ptr(a2), _lib.fptr(_c(w1)), None,
+        _lib.launch(_node_entry(E, "chain"), z2, _lib.ptr(t), _lib.ptr(a1), _lib.ptr(a2), _lib.fptr(_c(w1)), None,
                     _lib.fptr(_c(w2)), None, _lib.ptr(u1), _lib.ptr(u2), R, E, ctx.act)
         gw1 = gw2 = None
         if not _inputs_only():
-            gw1, _ = _wgrad(g1, t, False)
+            gw1, _ = _node_wgrad1(g1, t, False)
             gw2, _ = _wgrad(g2, u1, False)
         # act'' = 0: nothing reaches the forward's activations or z
         return u2.view(ctx.gshape), None, None, None, gw1, gw2, None, None, None
@@ -151,7 +179,7 @@ def _chain_act_ok(act_name) -> bool:
 
 
 def node_embed_supported(z, l1, l2, act_name) -> bool:
-    return (z.is_cuda and z.dtype == torch.float32 and _chain_act_ok(act_name) and 1 <= z.shape[-1] <= 16
+    return (z.is_cuda and z.dtype == torch.float32 and _chain_act_ok(act_name) and 1 <= z.shape[-1] <= 255
             and tuple(l1.weight.shape) == (64, z.shape[-1]) and tuple(l2.weight.shape) == (128, 64)
             and l1.bias is not None and l2.bias is not None and l1.weight.dtype == torch.float32)
 
@@ -257,7 +285,7 @@ def head_tail(z1, layers, act_name):
 
 def readout(x, weight, bias=None):
     """float32 ``F.linear(x.float(), weight, bias)`` for the Generator's readouts (dim 128 -> edge / node classes)."""
-    ok = (x.is_cuda and x.dtype in _lib.DTYPES and weight.dim() == 2 and weight.shape[1] == 128 and 1 <= weight.shape[0] <= 16
+    ok = (x.is_cuda and x.dtype in _lib.DTYPES and weight.dim() == 2 and weight.shape[1] == 128 and 1 <= weight.shape[0] <= 255
           and weight.dtype == torch.float32)
     if not ok:
         return linear(x.float(), weight, bias)
