@@ -185,6 +185,13 @@ NODE_WIDE_SIGNATURES = {
     "dg_wide_linear_wgrad": (c_int, [_P] * 5 + [c_size_t, c_int64, c_int, c_int, c_int, _P]),
 }
 
+# add-on entries of include/druggen_hip_row_gemm_any.h (same library): the float32 row GEMM for widths other than 128 / 384
+ROW_GEMM_ANY_SIGNATURES = {
+    "dg_row_gemm_any_packed_bytes": (c_size_t, [c_int, c_int]),
+    "dg_row_gemm_any_pack": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "dg_row_gemm_any": (c_int, [_P] * 4 + [c_int64, c_int, c_int, _P]),
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -207,7 +214,7 @@ def load() -> ctypes.CDLL:
                 "(druggen_amd has no CPU / eager fallback)")
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in {**SIGNATURES, **EMBED_KEEP_SIGNATURES, **EMBED_SMOOTH_SIGNATURES, **MOL_FEATURES_SIGNATURES,
-                                  **NODE_WIDE_SIGNATURES}.items():
+                                  **NODE_WIDE_SIGNATURES, **ROW_GEMM_ANY_SIGNATURES}.items():
             fn = getattr(lib, name)   # AttributeError if the .so lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = lib

@@ -138,12 +138,16 @@ def _wgrad_h16(dy2, x2, want_bias, ws=None):
 
 def _mm_rows(a, w, mode, bias=None):
     """a @ w^T (mode 0) or a @ w (mode 1) over the rows of ``a`` on dg_row_gemm when the shape is one
-    of its three, else on the ROCm BLAS (tiny / odd layers: embedding, readout, discriminator head).
+    of its three, on dg_row_gemm_any for float32 rows at the other widths that are multiples of 32 (--dim / --mlp_ratio
+    models), else on the ROCm BLAS (tiny / odd layers: embedding, readout, discriminator head; bfloat16 at other widths).
     The result has ``a``'s dtype (float32 or bfloat16 activations; parameters are float32)."""
     rows, cols = w.shape
     K, N = (cols, rows) if mode == 0 else (rows, cols)
     if a.is_cuda and a.dtype in _lib.DTYPES and row_gemm_supported(K, N):
         out = row_gemm(_c(a).reshape(-1, K), packed_weight(w, mode, a.dtype), K, N, bias=bias)
+        return out.view(*a.shape[:-1], N)
+    if a.is_cuda and a.dtype == torch.float32 and w.dtype == torch.float32 and any_gemm_supported(K, N):
+        out = row_gemm_any(_c(a).reshape(-1, K), packed_weight_any(w, mode), K, N, bias=bias)
         return out.view(*a.shape[:-1], N)
     if a.dtype != w.dtype:
         w = w.to(a.dtype)
@@ -362,6 +366,38 @@ def _repack_entries(entries, dtype) -> int:
 
 def row_gemm_supported(K: int, N: int) -> bool:
     return (K == 128 and N in (128, 384)) or (K == 384 and N == 128)
+
+
+def any_gemm_supported(K: int, N: int) -> bool:
+    """The shapes ``_mm_rows`` sends to dg_row_gemm_any: multiples of 32 in [32, 1024] that dg_row_gemm does not own
+    (``options.row_gemm_any`` False: none -- the equivalence tests' and A/B measurements' hook)."""
+    return (options.row_gemm_any and K % 32 == 0 and N % 32 == 0 and 32 <= K <= 1024 and 32 <= N <= 1024
+            and not row_gemm_supported(K, N))
+
+
+def packed_weight_any(w, mode: int):
+    """``packed_weight`` for dg_row_gemm_any (float32 rows): the same cache, under (id(w), mode, "any")."""
+    def make(w):
+        lib = _lib.load()
+        rows, cols = w.shape
+        n_out, k = (rows, cols) if mode == 0 else (cols, rows)
+        packed = torch.empty(int(lib.dg_row_gemm_any_packed_bytes(n_out, k)), dtype=torch.uint8, device=w.device)
+        wd = _c(w.detach())
+        _lib.launch("dg_row_gemm_any_pack", w, _lib.fptr(wd), packed.data_ptr(), rows, cols, mode)
+        return packed
+    return _pack_cache.get((w,), (mode, "any"), make)
+
+
+def row_gemm_any(a2, packed, K, N, bias=None):
+    """y [R,N] = a2 [R,K] @ B (+ bias) on dg_row_gemm_any (include/druggen_hip_row_gemm_any.h); float32."""
+    R = a2.shape[0]
+    y = torch.empty(R, N, dtype=torch.float32, device=a2.device)
+    if R == 0:      # (an empty tensor has no address to hand over)
+        return y
+    _lib.launch("dg_row_gemm_any", a2, _lib.fptr(a2), packed.data_ptr(), _lib.fptr(bias), _lib.fptr(y), R, K, N)
+    _pair_hold(a2, packed, bias, y)
+    _account("row_gemm_any", 4 * R * (K + N), 2 * R * K * N)
+    return y
 
 
 def row_gemm(a2, packed, K, N, bias=None, relu=False, want_relu_bits=False, mask_bits=None, residual=None, ln=None,

@@ -40,6 +40,7 @@ _CHOICES = {
     "penalty_wgrad": ("joined", "engine"), # the penalty's second-order parameter gradients joined in the forward node
     "embed_bf16": ("fast", "general"),     # bf16 edge-embedding backward: streaming kernel or the general one
     "embed_keep": (True, False),           # relu / leaky edge embedding: the forward keeps its signs, the backwards read them
+    "row_gemm_any": (True, False),         # float32 nn.Linear of other widths than 128 / 384 on dg_row_gemm_any (False: ROCm BLAS)
 }
 _ENV = {"hidden": "DG_HIDDEN", "ffn_f32": "DG_FFN_F32", "attn_half_f32": "DG_ATTN_HALF_F32",
         "attn_half_f32_bwd": "DG_ATTN_HALF_F32_BWD", "attn_half": "DG_ATTN_HALF", "ffn_bf16": "DG_FFN_BF16",
