@@ -192,6 +192,12 @@ ROW_GEMM_ANY_SIGNATURES = {
     "dg_row_gemm_any": (c_int, [_P] * 4 + [c_int64, c_int, c_int, _P]),
 }
 
+# add-on entries of include/druggen_hip_mol_stats.h (same library): per-molecule statistics of a decoded batch
+MOL_STATS_SIGNATURES = {
+    "dg_mol_stats_workspace_bytes": (c_size_t, [c_int]),
+    "dg_mol_stats": (c_int, [_P] * 9 + [c_int] * 5 + [_P, _P, _P, c_size_t, _P]),
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -214,7 +220,7 @@ def load() -> ctypes.CDLL:
                 "(druggen_amd has no CPU / eager fallback)")
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in {**SIGNATURES, **EMBED_KEEP_SIGNATURES, **EMBED_SMOOTH_SIGNATURES, **MOL_FEATURES_SIGNATURES,
-                                  **NODE_WIDE_SIGNATURES, **ROW_GEMM_ANY_SIGNATURES}.items():
+                                  **NODE_WIDE_SIGNATURES, **ROW_GEMM_ANY_SIGNATURES, **MOL_STATS_SIGNATURES}.items():
             fn = getattr(lib, name)   # AttributeError if the .so lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = lib

@@ -78,10 +78,17 @@ class ResidentTrainer:
 
     The graphed route refuses live dropout (the captured step shares one generator forward between the D and the G step) and
     restores the weights and the AdamW state after the capture's warm-up iterations, so both routes start from the weights
-    they were given."""
+    they were given.
+
+    ``monitor=`` a ``monitor.StepMonitor`` or ``True`` (a default one; the stepper's own if it has one): every step decodes the
+    generated batch and counts its statistics on the device (``GANStep.set_monitor``), and one device-side copy per step files
+    ``MolStats.tot`` into an ``[steps, 16]`` int64 device tensor per epoch (``monitor_totals``: the running epoch's, then the last
+    one's) beside the loss history.  ``fit`` / ``run_epoch`` hand it to ``on_monitor`` at the boundaries where ``on_log`` fires.
+    Under a process group each rank watches its own shard: duplicates are counted within the shard and no collective is added.
+    ``monitor=None``: nothing is allocated or launched."""
 
     def __init__(self, stepper: GANStep, molecules, drugs=None, *, batch_size: int, submodel: str = "DrugGEN",
-                 graph: bool = True, seed: int = 0, eps=None, log_every=None):
+                 graph: bool = True, seed: int = 0, eps=None, log_every=None, monitor=None):
         if submodel not in ("DrugGEN", "NoTarget"):
             raise ValueError(f"submodel must be 'DrugGEN' or 'NoTarget', got {submodel!r}")
         if submodel == "DrugGEN" and drugs is None:
@@ -109,6 +116,13 @@ class ResidentTrainer:
         self.epoch = 0
         b, N, M, E = self.batch_size // self.world, molecules.vertexes, molecules.m_dim, molecules.b_dim
         self.graphed = None
+        if monitor is True:
+            from .monitor import StepMonitor
+            monitor = stepper.monitor if stepper.monitor is not None else StepMonitor()
+        if monitor is not None and monitor is not stepper.monitor:
+            stepper.set_monitor(monitor)      # before the capture: the decode and the statistics are part of the graph
+        self.monitor = monitor
+        self.monitor_totals = None
         if graph:
             if _live_dropout(stepper.G) or _live_dropout(stepper.D):
                 raise RuntimeError("ResidentTrainer(graph=True): a model is training with dropout > 0 and the captured step "
@@ -155,29 +169,38 @@ class ResidentTrainer:
         for store in self.stores:
             store.raise_bad_indices(wait=wait)
 
-    def run_epoch(self, on_log=None, save_dir=None):
-        """One epoch; returns its ``[steps, 2]`` float32 device tensor of ``(d_loss, g_loss)``.  ``on_log`` / ``save_dir``: see
-        ``fit``."""
+    def run_epoch(self, on_log=None, save_dir=None, on_monitor=None):
+        """One epoch; returns its ``[steps, 2]`` float32 device tensor of ``(d_loss, g_loss)``.  ``on_log`` / ``save_dir`` /
+        ``on_monitor``: see ``fit``."""
         epoch, steps = self.epoch, self.steps_per_epoch
         history = torch.zeros(steps, 2, dtype=torch.float32, device=self.device)
+        if self.monitor is not None:
+            self.monitor_totals = torch.zeros(steps, 16, dtype=torch.int64, device=self.device)
         for i, (mol_idx, drug_idx) in enumerate(self.schedule()):
             torch.stack(self.step(mol_idx, drug_idx), out=history[i])
+            if self.monitor is not None:
+                self.monitor_totals[i].copy_(self.monitor.stats.tot)
             if self.log_every is not None and (i + 1) % self.log_every == 0 and i + 1 < steps:
-                self._boundary(epoch, i, history, on_log, save_dir)
+                self._boundary(epoch, i, history, on_log, save_dir, on_monitor)
         self.epoch += 1
         self._raise_bad_indices(wait=True)
-        self._boundary(epoch, steps - 1, history, on_log, save_dir)
+        self._boundary(epoch, steps - 1, history, on_log, save_dir, on_monitor)
         return history
 
-    def _boundary(self, epoch, i, history, on_log, save_dir):
+    def _boundary(self, epoch, i, history, on_log, save_dir, on_monitor=None):
         self._raise_bad_indices()
         if on_log is not None:
             on_log(epoch, i, history[:i + 1].cpu())
+        if on_monitor is not None and self.monitor is not None:
+            on_monitor(epoch, i, self.monitor_totals[:i + 1].cpu(), self.monitor.decoded.cpu())
         if save_dir is not None and self.rank == 0:
             checkpoint.save_model(self.stepper.G, self.stepper.D, save_dir, epoch, i)
 
-    def fit(self, epochs: int, on_log=None, save_dir=None):
+    def fit(self, epochs: int, on_log=None, save_dir=None, on_monitor=None):
         """``epochs`` epochs.  Every ``log_every`` steps and at the end of each epoch: ``on_log(epoch, step, losses_so_far)``
         with the epoch's losses so far as a host tensor ``[step + 1, 2]``, and with ``save_dir`` a checkpoint in the
-        reference's format (``checkpoint.save_model``, rank 0; ``train.py:386-397``).  Returns the per-epoch loss tensors."""
-        return [self.run_epoch(on_log, save_dir) for _ in range(int(epochs))]
+        reference's format (``checkpoint.save_model``, rank 0; ``train.py:386-397``).  With ``monitor=``, at the same boundaries:
+        ``on_monitor(epoch, step, totals_host, decoded_host)`` -- the epoch's ``MolStats.tot`` rows so far as a host tensor
+        ``[step + 1, 16]`` (``monitor.TOT_FIELDS``, ``monitor.fractions_of``) and the host ``MoleculeBatch`` of step ``step``, the
+        batch the last row counts (for RDKit on exactly those molecules).  Returns the per-epoch loss tensors."""
+        return [self.run_epoch(on_log, save_dir, on_monitor) for _ in range(int(epochs))]

@@ -101,7 +101,7 @@ class GANStep:
                  betas: Sequence[float] = (0.9, 0.999), lambda_gp: float = 10.0, group=None,
                  skip_d_wgrad_in_g_step: bool = True, d_loss_fn=discriminator_loss, g_loss_fn=generator_loss,
                  optimizer: str = "auto", share_generator_forward: bool = True, memory: str = "auto",
-                 split_d_backward: bool = True):
+                 split_d_backward: bool = True, monitor=None):
         self.G, self.D = G, D
         # the critic terms and the penalty are differentiated by two backward passes joined by ONE multi-tensor add (False: the
         # reference's single backward over their sum, for users of per-parameter hooks on D)
@@ -144,6 +144,32 @@ class GANStep:
         # launch stream; None = off)
         self.collective_events = None
         self._reduce_hook = None      # set by GraphedGANStep while it captures a data-parallel step in segments
+        # monitor.StepMonitor: decode the generated batch the D step sees and count its statistics, inside every step
+        self.monitor = None
+        if monitor is not None:
+            self.set_monitor(monitor)
+
+    def set_monitor(self, monitor) -> None:
+        """Attach a ``monitor.StepMonitor`` (None detaches it).  Right after the generator forward the D step uses -- the
+        pre-update generator, what the reference's ``logging()`` sees -- every step then runs ``decode_molecule_graphs`` into
+        ``monitor.decoded`` and ``molecule_statistics`` into ``monitor.stats`` on the launch stream, with the step's input atoms
+        and bond labels (inputs without attached one-hot labels: the two ``changed_*`` columns are -1).  Attach it before a
+        ``GraphedGANStep`` captures the step: the two calls become part of the graph (of its first segment under a process
+        group, where each rank counts its own shard)."""
+        if monitor is not None:
+            if self._d_loss_fn is not discriminator_loss or self._g_loss_fn is not generator_loss:
+                raise ValueError("monitor= reads the logits of the generator forward that the default discriminator_loss / "
+                                 "generator_loss share: it cannot watch a custom d_loss_fn / g_loss_fn")
+            if not self.share_generator_forward:
+                raise ValueError("monitor= reads the logits of the shared generator forward: it cannot watch a step with "
+                                 "share_generator_forward=False")
+            if self.G.training and float(getattr(self.G, "dropout", 0.0) or 0.0) > 0.0:
+                raise ValueError("monitor= reads the logits of the ONE generator forward both steps share: it cannot watch a "
+                                 "generator that is training with dropout > 0 (that one runs once per loss)")
+        self.monitor = monitor
+
+    def _observe(self, outputs, gen_edge, gen_node) -> None:
+        self.monitor.observe(outputs[0].detach(), outputs[1].detach(), gen_node, one_hot_labels(gen_edge))
 
     def time_collectives(self, on: bool = True) -> None:
         """Start (or stop) recording a pair of HIP events around every gradient all-reduce."""
@@ -279,12 +305,22 @@ class GANStep:
             if self._low_memory_shares_generator(gen_edge):      # one generator forward for both steps, as in the fast step
                 shared = self.G(gen_edge, gen_node)
                 samples = (shared[2].detach(), shared[3].detach())
+            elif self.monitor is not None:      # the forward _d_step_low_memory would run itself, made here to be watched
+                with torch.no_grad():
+                    samples = tuple(self.G(gen_edge, gen_node)[2:4])
+            if self.monitor is not None:
+                self._observe(samples, gen_edge, gen_node)
             d_loss = self._d_step_low_memory(disc_edge, disc_node, gen_edge, gen_node, B, dev, eps, samples)
         elif (self.share_generator_forward and self._d_loss_fn is discriminator_loss
                 and self._g_loss_fn is generator_loss
                 and not (self.G.training and float(getattr(self.G, "dropout", 0.0) or 0.0) > 0.0)):
             shared = self.G(gen_edge, gen_node)
             kw["generator_outputs"] = shared
+            if self.monitor is not None:
+                self._observe(shared[2:4], gen_edge, gen_node)
+        elif self.monitor is not None:
+            raise RuntimeError("GANStep(monitor=...): this step runs the generator once per loss (the generator is training with "
+                               "dropout > 0), so there is no shared forward to watch")
         if not low and self._d_loss_fn is discriminator_loss and self.split_d_backward:
             # The critic terms and the penalty share nothing but D's parameters.  One backward over their sum makes the
             # autograd engine add the two contributions of every parameter with a kernel of its own (~140 tiny adds per
