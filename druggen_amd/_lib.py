@@ -64,38 +64,30 @@ SIGNATURES = {
     "dg_ln_residual_bwd2": (c_int, [_P] * 10 + [_P, c_size_t, c_int64, c_int, c_int, _P]),
     "dg_linear_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "dg_linear_wgrad": (c_int, [_P] * 5 + [_P, c_size_t, c_int64, c_int, c_int, c_int, _P]),
-    "dg_row_gemm_packed_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "dg_row_gemm_pack": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
-    "dg_row_gemm_mask_words": (c_size_t, [c_int64, c_int, c_int, c_int]),
-    "dg_row_gemm": (c_int, [_P] * 3 + [c_int64, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_float, c_int, _P]),
     "dg_linear_wgrad3": (c_int, [_P] * 6 + [_P, c_size_t, c_int64, c_int, _P]),
-    "dg_row_gemm_pack3": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
-    "dg_row_gemm_lin3": (c_int, [_P] * 5 + [c_int64, _P, _P, _P, c_int, _P]),
-    "dg_row_gemm_sum3": (c_int, [_P] * 5 + [c_int64, _P, c_int, _P]),
     "dg_linear_wgrad_batch_begin": (c_int, []),
     "dg_linear_wgrad_batch_end": (c_int, [_P]),
     "dg_launch_pair_begin": (c_int, []),
     "dg_launch_pair_end": (c_int, [_P]),
-    "dg_skinny_linear_fwd": (c_int, [_P] * 4 + [c_int64, c_int, c_int, c_int, _P]),
-    "dg_skinny_linear_dgrad": (c_int, [_P] * 3 + [c_int64, c_int, c_int, c_int, _P]),
-    "dg_skinny_linear_wgrad": (c_int, [_P] * 5 + [c_size_t, c_int64, c_int, c_int, c_int, _P]),
-    "dg_embed_node_chain": (c_int, [_P] * 9 + [c_int64, c_int, c_int, _P]),
-    "dg_embed_node_bwd": (c_int, [_P] * 8 + [c_int64, c_int, c_int, _P]),
-    "dg_head_chain": (c_int, [_P] * 14 + [c_int64, c_int, _P]),
-    "dg_head_bwd": (c_int, [_P] * 10 + [c_int64, c_int, _P]),
-    "dg_head_wgrad": (c_int, [_P] * 12 + [c_int64, _P]),
+    "dg_row_gemm_packed_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dg_row_gemm_pack": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
     "dg_row_gemm_pack_batch": (c_int, [_P, c_int, c_int, c_int, _P]),
+    "dg_row_gemm_pack3": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "dg_row_gemm_lin3": (c_int, [_P] * 5 + [c_int64, _P, _P, _P, c_int, _P]),
+    "dg_row_gemm_sum3": (c_int, [_P] * 5 + [c_int64, _P, c_int, _P]),
+    "dg_row_gemm_mask_words": (c_size_t, [c_int64, c_int, c_int, c_int]),
+    "dg_row_gemm": (c_int, [_P] * 3 + [c_int64, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_float, c_int, _P]),
     "dg_row_gemm_ln_bwd_workspace_bytes": (c_size_t, [c_int]),
     "dg_row_gemm_ln_bwd": (c_int, [_P] * 3 + [c_int64, c_int] + [_P] * 7 + [_P, c_size_t, c_int, _P]),
     "dg_row_gemm_ln_bwd_in": (c_int, [_P] * 10 + [_P, c_size_t, c_int64, c_int, c_int, c_int, _P]),
+    "dg_row_gemm_any_packed_bytes": (c_size_t, [c_int, c_int]),
+    "dg_row_gemm_any_pack": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "dg_row_gemm_any": (c_int, [_P] * 4 + [c_int64, c_int, c_int, _P]),
     "dg_edge_ffn_ln_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "dg_edge_ffn_ln_fwd": (c_int, [_P] * 13 + [c_int64, c_int, c_int, c_float, c_int, _P]),
     "dg_edge_ffn_ln_bwd": (c_int, [_P] * 20 + [_P, c_size_t, c_int64, c_int, c_int, c_int, _P]),
     "dg_edge_ffn_ln_fwd_pair": (c_int, [ctypes.POINTER(FFNFwdArgs), ctypes.POINTER(FFNFwdArgs), c_int, c_int, c_int, _P]),
     "dg_edge_ffn_ln_bwd_pair": (c_int, [ctypes.POINTER(FFNBwdArgs), ctypes.POINTER(FFNBwdArgs), c_int, c_int, c_int, _P]),
-    "dg_ffn_f32_packed_bytes": (c_size_t, []),
-    "dg_ffn_f32_pack": (c_int, [_P, _P, _P, _P]),
-    "dg_ffn_ln_fwd_f32": (c_int, [ctypes.POINTER(FFNFwdArgs), ctypes.POINTER(FFNFwdArgs), _P]),
     "dg_ffn_bf16_padded_rows": (c_int64, [c_int64]),
     "dg_ffn_bf16_packed_bytes": (c_size_t, []),
     "dg_ffn_bf16_pack": (c_int, [_P, _P, _P, _P]),
@@ -103,33 +95,60 @@ SIGNATURES = {
     "dg_ffn_bf16_workspace_bytes": (c_size_t, [c_int64]),
     "dg_ffn_ln_fwd_bf16": (c_int, [_P] * 11 + [c_int64, c_float, _P]),
     "dg_ffn_ln_bwd_bf16": (c_int, [_P] * 18 + [_P, c_size_t, c_int64, _P]),
+    "dg_ffn_f32_packed_bytes": (c_size_t, []),
+    "dg_ffn_f32_pack": (c_int, [_P, _P, _P, _P]),
+    "dg_ffn_ln_fwd_f32": (c_int, [ctypes.POINTER(FFNFwdArgs), ctypes.POINTER(FFNFwdArgs), _P]),
     "dg_embed_sym_packed_floats": (c_size_t, []),
     "dg_embed_sym_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "dg_embed_sym_pack": (c_int, [_P, _P, _P]),
     "dg_embed_sym_dgrad_packed_floats": (c_size_t, []),
     "dg_embed_sym_pack_dgrad": (c_int, [_P, _P, _P]),
-    "dg_embed_sym_pack": (c_int, [_P, _P, _P]),
     "dg_embed_sym_fwd": (c_int, [_P] * 6 + [c_int] * 7 + [_P]),
     "dg_embed_sym_bwd": (c_int, [_P] * 12 + [_P, c_size_t] + [c_int] * 7 + [_P]),
     "dg_embed_sym_bwd_bf16_workspace_bytes": (c_size_t, [c_int, c_int]),
     "dg_embed_sym_bwd_bf16": (c_int, [_P] * 11 + [_P, c_size_t] + [c_int] * 6 + [_P]),
     "dg_embed_sym_bwd2": (c_int, [_P] * 11 + [_P, c_size_t] + [c_int] * 7 + [_P]),
+    "dg_embed_sym_sign_words": (c_size_t, [c_int, c_int]),
+    "dg_embed_sym_fwd_keep": (c_int, [_P] * 7 + [c_int] * 7 + [_P]),
+    "dg_embed_sym_bwd_keep": (c_int, [_P] * 13 + [_P, c_size_t] + [c_int] * 7 + [_P]),
+    "dg_embed_sym_bwd2_keep": (c_int, [_P] * 12 + [_P, c_size_t] + [c_int] * 7 + [_P]),
+    "dg_embed_sym_bwd2_smooth": (c_int, [_P] * 14 + [_P, c_size_t] + [c_int] * 7 + [_P]),
     "dg_onehot_embed_workspace_bytes": (c_size_t, [c_int, c_int]),
     "dg_onehot_embed_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "dg_onehot_embed_bwd": (c_int, [_P, _P, _P, _P, c_size_t, c_int, c_int, c_int, c_int, c_int, _P]),
     "dg_densify": (c_int, [_P, _P, _P, c_int64, c_int, c_int, c_int, _P, _P, _P, _P]),
     "dg_mol_gather": (c_int, [_P, _P, _P, c_int64, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    "dg_mol_gather_features": (c_int, [_P, _P, _P, _P, c_int64, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "dg_adamw_flat": (c_int, [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float, c_int64, _P]),
     "dg_adamw_flat_devstep": (c_int, [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float, _P, _P]),
+    "dg_skinny_linear_fwd": (c_int, [_P] * 4 + [c_int64, c_int, c_int, c_int, _P]),
+    "dg_skinny_linear_dgrad": (c_int, [_P] * 3 + [c_int64, c_int, c_int, c_int, _P]),
+    "dg_skinny_linear_wgrad": (c_int, [_P] * 5 + [c_size_t, c_int64, c_int, c_int, c_int, _P]),
+    "dg_wide_linear_fwd": (c_int, [_P] * 4 + [c_int64, c_int, c_int, c_int, _P]),
+    "dg_wide_linear_dgrad": (c_int, [_P] * 3 + [c_int64, c_int, c_int, c_int, _P]),
+    "dg_wide_linear_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "dg_wide_linear_wgrad": (c_int, [_P] * 5 + [c_size_t, c_int64, c_int, c_int, c_int, _P]),
+    "dg_head_chain": (c_int, [_P] * 14 + [c_int64, c_int, _P]),
+    "dg_head_bwd": (c_int, [_P] * 10 + [c_int64, c_int, _P]),
+    "dg_head_wgrad": (c_int, [_P] * 12 + [c_int64, _P]),
+    "dg_embed_node_chain": (c_int, [_P] * 9 + [c_int64, c_int, c_int, _P]),
+    "dg_embed_node_bwd": (c_int, [_P] * 8 + [c_int64, c_int, c_int, _P]),
+    "dg_embed_node_wide_chain": (c_int, [_P] * 9 + [c_int64, c_int, c_int, _P]),
+    "dg_embed_node_wide_bwd": (c_int, [_P] * 8 + [c_int64, c_int, c_int, _P]),
+    "dg_embed_node_wide_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "dg_embed_node_wide_wgrad": (c_int, [_P] * 5 + [c_size_t, c_int64, c_int, _P]),
     "dg_argmax_decode": (c_int, [_P, c_int64, c_int, _P, _P]),
     "dg_decode_graph": (c_int, [_P] * 3 + [c_int] * 5 + [_P] * 8 + [_P]),
+    "dg_mol_stats_workspace_bytes": (c_size_t, [c_int]),
+    "dg_mol_stats": (c_int, [_P] * 9 + [c_int] * 5 + [_P, _P, _P, c_size_t, _P]),
     "dg_fp_pack": (c_int, [_P, c_int, c_int64, c_int, _P, _P, _P]),
     "dg_fp_tanimoto_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "dg_fp_tanimoto": (c_int, [_P, _P, c_int64, _P, _P, c_int64, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "dg_prof_enable": (c_int, [c_int]),
     "dg_prof_reset": (c_int, []),
-    "dg_prof_read": (c_int, [c_int, ctypes.POINTER(c_int64), ctypes.POINTER(c_double)]),
     "dg_set_edge_rows": (c_int, [c_int64]),
     "dg_edge_rows": (c_int64, []),
+    "dg_prof_read": (c_int, [c_int, ctypes.POINTER(c_int64), ctypes.POINTER(c_double)]),
 }
 
 KERNEL_IDS = {"attn_fwd": 0, "attn_bwd": 1, "attn_bwd2": 2, "ln_fwd": 3, "ln_bwd": 4, "ln_bwd2": 5, "linear_wgrad": 6, "row_gemm": 7, "embed_sym": 8, "ffn": 9, "ffn_wgrad": 10,
@@ -155,48 +174,6 @@ def set_edge_rows(rows: int = 0) -> None:
         check(load().dg_set_edge_rows(rows), "dg_set_edge_rows")
         _edge_rows = rows
 
-# add-on entries of include/druggen_hip_embed_keep.h (same library): the edge embedding on kept signs
-EMBED_KEEP_SIGNATURES = {
-    "dg_embed_sym_sign_words": (c_size_t, [c_int, c_int]),
-    "dg_embed_sym_fwd_keep": (c_int, [_P] * 7 + [c_int] * 7 + [_P]),
-    "dg_embed_sym_bwd_keep": (c_int, [_P] * 13 + [_P, c_size_t] + [c_int] * 7 + [_P]),
-    "dg_embed_sym_bwd2_keep": (c_int, [_P] * 12 + [_P, c_size_t] + [c_int] * 7 + [_P]),
-}
-
-# add-on entry of include/druggen_hip_embed_smooth.h (same library): the embedding's second order for sigmoid / tanh
-EMBED_SMOOTH_SIGNATURES = {
-    "dg_embed_sym_bwd2_smooth": (c_int, [_P] * 14 + [_P, c_size_t] + [c_int] * 7 + [_P]),
-}
-
-# add-on entry of include/druggen_hip_mol_features.h (same library): dg_mol_gather for a store with a feature plane
-MOL_FEATURES_SIGNATURES = {
-    "dg_mol_gather_features": (c_int, [_P, _P, _P, _P, c_int64, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
-}
-
-# add-on entries of include/druggen_hip_node_wide.h (same library): node embedding and node readout wider than 16 columns
-NODE_WIDE_SIGNATURES = {
-    "dg_embed_node_wide_chain": (c_int, [_P] * 9 + [c_int64, c_int, c_int, _P]),
-    "dg_embed_node_wide_bwd": (c_int, [_P] * 8 + [c_int64, c_int, c_int, _P]),
-    "dg_embed_node_wide_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int]),
-    "dg_embed_node_wide_wgrad": (c_int, [_P] * 5 + [c_size_t, c_int64, c_int, _P]),
-    "dg_wide_linear_fwd": (c_int, [_P] * 4 + [c_int64, c_int, c_int, c_int, _P]),
-    "dg_wide_linear_dgrad": (c_int, [_P] * 3 + [c_int64, c_int, c_int, c_int, _P]),
-    "dg_wide_linear_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
-    "dg_wide_linear_wgrad": (c_int, [_P] * 5 + [c_size_t, c_int64, c_int, c_int, c_int, _P]),
-}
-
-# add-on entries of include/druggen_hip_row_gemm_any.h (same library): the float32 row GEMM for widths other than 128 / 384
-ROW_GEMM_ANY_SIGNATURES = {
-    "dg_row_gemm_any_packed_bytes": (c_size_t, [c_int, c_int]),
-    "dg_row_gemm_any_pack": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
-    "dg_row_gemm_any": (c_int, [_P] * 4 + [c_int64, c_int, c_int, _P]),
-}
-
-# add-on entries of include/druggen_hip_mol_stats.h (same library): per-molecule statistics of a decoded batch
-MOL_STATS_SIGNATURES = {
-    "dg_mol_stats_workspace_bytes": (c_size_t, [c_int]),
-    "dg_mol_stats": (c_int, [_P] * 9 + [c_int] * 5 + [_P, _P, _P, c_size_t, _P]),
-}
 
 _lock = threading.Lock()
 _lib = None
@@ -219,8 +196,7 @@ def load() -> ctypes.CDLL:
                 f"{LIB_PATH} not found: build it with `python -m druggen_amd.build` "
                 "(druggen_amd has no CPU / eager fallback)")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**SIGNATURES, **EMBED_KEEP_SIGNATURES, **EMBED_SMOOTH_SIGNATURES, **MOL_FEATURES_SIGNATURES,
-                                  **NODE_WIDE_SIGNATURES, **ROW_GEMM_ANY_SIGNATURES, **MOL_STATS_SIGNATURES}.items():
+        for name, (res, args) in SIGNATURES.items():
             fn = getattr(lib, name)   # AttributeError if the .so lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = lib

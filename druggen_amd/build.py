@@ -25,16 +25,11 @@ def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
 
 
-def _public_headers():
-    """include/druggen_hip.h and its add-on headers."""
-    return sorted(glob.glob(os.path.join(os.path.dirname(HEADER), "*.h")))
-
-
 def _stale() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + _public_headers()
+    deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + [HEADER]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -46,7 +41,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         raise RuntimeError("hipcc not found: cannot build libdruggen_hip.so")
     os.makedirs(LIB_DIR, exist_ok=True)
     objs, jobs = [], []
-    headers = glob.glob(os.path.join(CSRC, "*.h")) + _public_headers()
+    headers = glob.glob(os.path.join(CSRC, "*.h")) + [HEADER]
     for src in sources():
         obj = os.path.join(LIB_DIR, os.path.basename(src) + ".o")
         objs.append(obj)

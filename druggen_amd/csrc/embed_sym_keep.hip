@@ -3,7 +3,6 @@
 // skip the stages of outputs that are not wanted.  Same tiles, products and summation orders: every output is bit-identical
 // to the entries of embed_sym.hip.
 #include "embed_sym.h"
-#include "../../include/druggen_hip_embed_keep.h"
 
 namespace dg {
 namespace {

@@ -16,7 +16,6 @@
 // first backward (on r1 instead of p1).  f' and f'' are taken through the outputs h1 and y that act_fwd gives, as in the
 // forward and the first backward.  s1 is recomputed from t where r1 is formed (E <= 16 multiply-adds), never q / f'.
 #include "embed_sym.h"
-#include "../../include/druggen_hip_embed_smooth.h"
 
 namespace dg {
 namespace {

@@ -17,7 +17,6 @@
 // x [B, N, M] is then one-hot(atoms) in the columns below atom_dim and the bits in the columns from atom_dim up.  The index,
 // label and `a` phases are gather_bonds() for both kernels; only the x stream differs.
 #include "common.h"
-#include "../../include/druggen_hip_mol_features.h"
 
 namespace dg {
 namespace {

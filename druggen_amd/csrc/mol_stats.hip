@@ -1,4 +1,4 @@
-// Per-molecule statistics of a decoded batch (include/druggen_hip_mol_stats.h): what the reference's
+// Per-molecule statistics of a decoded batch (dg_mol_stats of include/druggen_hip.h): what the reference's
 // logging() (src/util/utils.py:241-355) reads off the generated molecules that is integer arithmetic on the decoded labels
 // -- distinct atom types (Metrics.mean_atom_type, utils.py:112-127), over-valent atoms, positions that differ from the
 // step's input graph, and the first earlier molecule of the batch with the same decoded graph.  Integers only: every
@@ -11,8 +11,6 @@
 //   mol_stats_totals one workgroup: tot[16] from mol[B, 8]
 // Every element of mol and tot is stored by every call; the key workspace is rewritten before it is read.
 #include "common.h"
-
-#include "../../include/druggen_hip_mol_stats.h"
 
 namespace dg {
 namespace {

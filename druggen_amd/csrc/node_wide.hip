@@ -16,7 +16,6 @@
 // All arithmetic is float32 fmaf; no atomics: every result is a fixed sequence of operations.
 #include "bf16.h"
 #include "embed_node.h"
-#include "../../include/druggen_hip_node_wide.h"
 
 namespace dg {
 namespace {
@@ -339,7 +338,7 @@ int tile_grid(int64_t R) {
 
 using namespace dg;
 
-/* see include/druggen_hip_node_wide.h */
+/* see include/druggen_hip.h */
 extern "C" int dg_embed_node_wide_chain(const float* in, const float* m1, const float* m2, const float* w1, const float* b1,
                                         const float* w2, const float* b2, float* o1, float* o2, int64_t R, int E, int act,
                                         dg_stream_t stream_) {

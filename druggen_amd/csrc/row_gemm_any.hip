@@ -1,4 +1,4 @@
-// Row GEMM for any widths (include/druggen_hip_row_gemm_any.h): y [R,N] = a [R,K] . B (+ bias), float32 rows,
+// Row GEMM for any widths (dg_row_gemm_any* of include/druggen_hip.h): y [R,N] = a [R,K] . B (+ bias), float32 rows,
 // K and N multiples of 32 in [32, 1024] -- the nn.Linear layers of a model whose --dim / --mlp_ratio are not 128 / 3.
 //
 // Arithmetic of row_gemm.hip: fp16 hi + lo planes under an exact power-of-two scale per ROW of the activation and per output
@@ -22,7 +22,6 @@
 #include <climits>
 #include <type_traits>
 
-#include "../../include/druggen_hip_row_gemm_any.h"
 #include "f16_scale.h"
 #include "lane_reduce.h"
 

@@ -389,7 +389,7 @@ def packed_weight_any(w, mode: int):
 
 
 def row_gemm_any(a2, packed, K, N, bias=None):
-    """y [R,N] = a2 [R,K] @ B (+ bias) on dg_row_gemm_any (include/druggen_hip_row_gemm_any.h); float32."""
+    """y [R,N] = a2 [R,K] @ B (+ bias) on dg_row_gemm_any (include/druggen_hip.h); float32."""
     R = a2.shape[0]
     y = torch.empty(R, N, dtype=torch.float32, device=a2.device)
     if R == 0:      # (an empty tensor has no address to hand over)

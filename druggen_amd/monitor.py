@@ -3,7 +3,7 @@ that is integer arithmetic on the decoded labels, so that it can run inside ever
 ``log_sample_step``-th.
 
 ``molecule_statistics`` turns a device ``decode.MoleculeBatch`` into ``MolStats`` with one call of ``dg_mol_stats``
-(``include/druggen_hip_mol_stats.h``); ``StepMonitor`` owns the static buffers ``GANStep(monitor=...)`` decodes and counts into.
+(``include/druggen_hip.h``); ``StepMonitor`` owns the static buffers ``GANStep(monitor=...)`` decodes and counts into.
 Canonical SMILES, RDKit validity and fingerprints stay with the caller (``smiles.py``, ``metrics.py``).  GPU only, no CPU fallback."""
 from __future__ import annotations
 

@@ -25,7 +25,7 @@ are the ``atoms`` byte, the other ``F = m_dim - atom_dim`` columns must be exact
     store = ResidentMolecules.from_graphs(graphs, atom_dim=13)     # x [N, 13 + 54]: 9 bytes per atom position
     real_graphs, a_tensor, x_tensor = store.batch(idx)             # x_tensor [B, N, 67], as load_molecules returns it
 
-Such a store launches ``dg_mol_gather_features`` (include/druggen_hip_mol_features.h); everything else is the same.
+Such a store launches ``dg_mol_gather_features`` (include/druggen_hip.h); everything else is the same.
 
 GPU only, no CPU fallback (``pack`` and ``split_batch`` are host-side numpy)."""
 from __future__ import annotations

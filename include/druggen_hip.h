@@ -363,6 +363,24 @@ int dg_row_gemm_ln_bwd_in(const void* dy, const void* ln_pre, const float* ln_me
  * fp32 accumulate and epilogue arithmetic.  Bit masks are available for every shape in this mode (the
  * layout is private to the (K, N, dtype) triple: only pass a mask to a launch of the same triple).   */
 
+/* ---- float32 row GEMM for any widths: the nn.Linear layers whose widths are not the three dg_row_gemm owns (the reference's
+ * --dim / --mlp_ratio; csrc/row_gemm_any.hip).  Added after DG_VERSION 232 without a version bump.
+ * Same arithmetic class as dg_row_gemm for float32 rows: fp16 hi + lo planes under a power-of-two scale per activation row and
+ * per output channel, three MFMA products, float32 accumulation in a fixed order over K that does not depend on R -- results
+ * are bit-identical from run to run, and a row's result does not depend on the rows around it.                            */
+/* Bytes of the packed copy of a weight with n_out output channels and a contraction of k: both multiples of 32 in
+ * [32, 1024]; 0 for any other shape.                                                                                      */
+size_t dg_row_gemm_any_packed_bytes(int n_out, int k);
+/* Pack the float32 nn.Linear weight w [rows, cols] into MFMA fragment order (hi / lo planes, inverse channel scales).
+ * mode 0: the forward operand (y = a w^T: n_out = rows, k = cols); mode 1: the input-gradient operand (y = a w: n_out = cols,
+ * k = rows).  Null w / packed or another mode: DG_E_ARG; rows / cols not a multiple of 32 in [32, 1024]: DG_E_SHAPE.       */
+int dg_row_gemm_any_pack(const float* w, void* packed, int rows, int cols, int mode, dg_stream_t stream);
+/* y [R,N] = a [R,K] . B (+ bias [N]; bias may be NULL) with B the operand packed for (n_out = N, k = K).  Null a / packed / y:
+ * DG_E_ARG; R < 0, or K / N not a multiple of 32 in [32, 1024]: DG_E_SHAPE; R == 0 returns 0 without a launch.  The three
+ * shapes of dg_row_gemm are served too (with a pack made by dg_row_gemm_any_pack).                                         */
+int dg_row_gemm_any(const float* a, const void* packed, const float* bias, float* y, int64_t R, int K, int N,
+                    dg_stream_t stream);
+
 /* ---- feed-forward half of an Encoder_Block: src/model/layers.py:191-192 + MLP (:40-54) ----
  *   y = LayerNorm(x + fc2(relu(fc1(x)))) * gamma + beta      (dim C = 128, hidden H = 384)
  * One call per direction; internally the row-GEMM / LayerNorm / weight-gradient kernels above,
@@ -495,10 +513,50 @@ int dg_embed_sym_bwd2(const float* a, const float* w1, const float* b1, const fl
                       void* gg, float* gw1, float* gw2, void* workspace, size_t workspace_bytes,
                       int B, int N, int E, int H, int C, int act, int dtype, dg_stream_t stream);
 
-/* The same three entries with the forward's signs KEPT instead of recomputed (relu / leaky): druggen_hip_embed_keep.h,
- * an add-on header next to this one.  The entries above are unchanged.                                          */
-/* The second order for the smooth activations (sigmoid / tanh, act'' != 0: dg_embed_sym_bwd2_smooth):
- * druggen_hip_embed_smooth.h, an add-on header next to this one.                                                */
+/* The same three entries with the forward's signs KEPT instead of recomputed (csrc/embed_sym_keep.hip), for the
+ * piecewise-linear activations (act = relu, leaky; others: DG_E_ARG).  Added after DG_VERSION 232 without a version bump: the
+ * entries above are unchanged.
+ * `signs`: dg_embed_sym_sign_words(B, N) uint32 words, six per edge row r = (b N + i) N + j at signs[6 r ..]:
+ *   words 0..3: bit (c & 31) of word (c >> 5) is set iff the layer-2 pre-activation (bias included) of channel c is > 0,
+ *   words 4..5: bit (u & 31) of word 4 + (u >> 5) is set iff the layer-1 pre-activation of hidden unit u is > 0.
+ * _fwd_keep writes the output of dg_embed_sym_fwd (bit for bit) and every word of `signs`.  _bwd_keep and _bwd2_keep
+ * read the signs in place of both recomputed layers and return, bit for bit, what _bwd / _bwd2 return -- for the outputs
+ * that are wanted: da may be NULL; dw1, db1, dw2, db2 are all non-NULL or all NULL (a mixture: DG_E_ARG; nothing wanted:
+ * 0 without a launch); gw1, gw2 are both non-NULL or both NULL.  Without weight gradients _bwd_keep reads neither `a` nor
+ * the workspace, and _bwd2_keep reads neither `a` nor `g`; the pointers are still checked.                           */
+size_t dg_embed_sym_sign_words(int B, int N);
+int dg_embed_sym_fwd_keep(const float* a, const float* w1, const float* b1, const float* w2_packed, const float* b2,
+                          void* out, uint32_t* signs, int B, int N, int E, int H, int C, int act, int dtype,
+                          dg_stream_t stream);
+int dg_embed_sym_bwd_keep(const float* a, const float* w1, const float* b1, const float* w2_packed,
+                          const float* w2_dgrad_packed, const float* b2, const void* g, const uint32_t* signs,
+                          float* da, float* dw1, float* db1, float* dw2, float* db2,
+                          void* workspace, size_t workspace_bytes,
+                          int B, int N, int E, int H, int C, int act, int dtype, dg_stream_t stream);
+int dg_embed_sym_bwd2_keep(const float* a, const float* w1, const float* b1, const float* w2_packed,
+                           const float* w2_dgrad_packed, const float* b2, const void* g, const float* t,
+                           const uint32_t* signs, void* gg, float* gw1, float* gw2, void* workspace,
+                           size_t workspace_bytes, int B, int N, int E, int H, int C, int act, int dtype,
+                           dg_stream_t stream);
+
+/* Backward of dg_embed_sym_bwd for the gradient penalty, act = sigmoid (2) or tanh (3) (csrc/embed_sym_smooth.hip; added
+ * after DG_VERSION 232 without a version bump).  With act'' != 0 the adjoint t [B,N,N,E] of da reaches every operand of the
+ * forward, not only g, w1 and w2 as in dg_embed_sym_bwd2.  Per edge row, gs = the symmetrised upstream gradient, u1 / u2 =
+ * the pre-activations of the two layers, h1 = act(u1):
+ *   p2 = gs act'(u2), dh1 = W2^T p2, p1 = dh1 act'(u1)                          (the first backward, recomputed)
+ *   s1 = W1 t, q = s1 act'(u1), s2 = W2 q, x = s2 act'(u2)                      gg = (x_ij + x_ji) / 2
+ *   r2 = gs act''(u2) s2,  r1 = act''(u1) s1 dh1 + act'(u1) (W2^T r2)
+ *   gw2 = sum p2 q^T + r2 h1^T, gb2 = sum r2, gw1 = sum p1 t^T + r1 a^T, gb1 = sum r1, ga = W1^T r1 (per row)
+ * Operands as dg_embed_sym_bwd2.  Outputs: gg [B,N,N,C] (dtype) = adjoint of g; ga [B,N,N,E] = adjoint of a (fp32, may be
+ * NULL); gw1 [H,E], gb1 [H], gw2 [C,H], gb2 [C] (fp32): all four non-NULL or all four NULL (a mixture: DG_E_ARG).  NULL
+ * skips the stages of that output, and for the parameters the reduction and the workspace too; what remains is bit for
+ * bit what the full call returns.  Workspace: dg_embed_sym_workspace_bytes(B, N) (too small: DG_E_WORKSPACE).  act = relu,
+ * leaky: DG_E_ARG (dg_embed_sym_bwd2 is their entry).  No atomics; the grid is fixed by the shape: bit-reproducible.   */
+int dg_embed_sym_bwd2_smooth(const float* a, const float* w1, const float* b1, const float* w2_packed,
+                             const float* w2_dgrad_packed, const float* b2, const void* g, const float* t,
+                             void* gg, float* ga, float* gw1, float* gb1, float* gw2, float* gb2,
+                             void* workspace, size_t workspace_bytes,
+                             int B, int N, int E, int H, int C, int act, int dtype, dg_stream_t stream);
 
 /* One-hot fast path of the same op (reference src/data/utils.py:15-23 makes the generator's input and the
  * discriminator's real batch one-hot): with labels l [B,N,N] (int32, 0 <= l < E) and the E x C table
@@ -544,6 +602,22 @@ int dg_densify(const int64_t* edge_src, const int64_t* edge_dst, const int64_t* 
 int dg_mol_gather(const uint8_t* atoms, const int64_t* ptr, const uint32_t* entries, int64_t n, const int64_t* index, int B,
                   int N, int M, int E, float* a, int* labels, float* x, int* bad_index, dg_stream_t stream);
 
+/* dg_mol_gather for node matrices that are a one-hot atom type followed by F = M - atom_dim columns of exactly 0 or 1 (the
+ * reference's --features, dataset.py:305-307).  Added after DG_VERSION 232 without a version bump.  The store of
+ * dg_mol_gather plus
+ *   bits  [n, N, W]  u32  W = ceil(F / 32); feature column f of an atom position is bit f % 32 of word f / 32; the unused high
+ *                         bits of the last word are zero
+ * and each atoms[m, i] < atom_dim.  Outputs as dg_mol_gather, except
+ *   x  [B, N, M]  f32  x[b, i, c] = [atoms[m, i] == c] for c < atom_dim, bit c - atom_dim of bits[m, i, :] for c >= atom_dim
+ * with m = index[b].  EVERY element is written; `labels`, `a`, the clamping and counting of bad indices, the memset node on
+ * `bad_index` and the alignment rules (molecule bases 4-byte aligned) are dg_mol_gather's, and so is the code that does them.
+ * No load leaves the store's arrays.  Limits of dg_mol_gather, and 1 <= atom_dim <= M with W == ceil((M - atom_dim) / 32):
+ * others DG_E_SHAPE; B == 0 returns 0 without a launch; a null pointer (`bits` may be NULL only when W == 0) or a misaligned
+ * one (`bits`: 4 bytes): DG_E_ARG.                                                                                         */
+int dg_mol_gather_features(const uint8_t* atoms, const int64_t* ptr, const uint32_t* entries, const uint32_t* bits, int64_t n,
+                           const int64_t* index, int B, int N, int M, int E, int W, int atom_dim, float* a, int* labels,
+                           float* x, int* bad_index, dg_stream_t stream);
+
 /* dg_adamw_flat: one torch.optim.AdamW update (reference train.py:213-214,368,384;
  * decoupled weight decay, no amsgrad) over flat float32 buffers; `step` >= 1.       */
 int dg_adamw_flat(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
@@ -567,6 +641,21 @@ int dg_skinny_linear_dgrad(const float* dy, const float* w, void* dx, int64_t R,
 /* dw [N,K], db [N] (nullable) from float32 dy [R,N] and x [R,K] of `dtype`; workspace as for dg_linear_wgrad. */
 int dg_skinny_linear_wgrad(const float* dy, const void* x, float* dw, float* db, void* workspace, size_t workspace_bytes,
                            int64_t R, int N, int K, int dtype, dg_stream_t stream);
+
+/* Wide readout: nn.Linear(128 -> N), 17 <= N <= 255 (readout_n of a --features Generator, reference models.py:100-101;
+ * csrc/node_wide.hip; added after DG_VERSION 232 without a version bump), with the semantics of
+ * dg_skinny_linear_fwd / _dgrad / _wgrad: x [R,128] in the activation dtype (`dtype`: DG_DTYPE_F32 or DG_DTYPE_BF16),
+ * w [N,128], b [N] or NULL, y [R,N] float32; _dgrad: dx [R,128] (activation dtype) = dy [R,N] (float32) . w;
+ * _wgrad: dw [N,128] = dy^T x, db [N] (nullable) = column sums of dy, partial sums in `workspace`
+ * (dg_wide_linear_wgrad_workspace_bytes(R, N, K)) as for dg_embed_node_wide_wgrad.  K != 128 or N outside 17..255: DG_E_SHAPE;
+ * R == 0 returns 0 without a launch (_fwd, _dgrad; _wgrad needs R >= 1).  float32 fmaf arithmetic without atomics: results
+ * are bit-identical from run to run.                                                                                          */
+int dg_wide_linear_fwd(const void* x, const float* w, const float* b, float* y, int64_t R, int N, int K, int dtype,
+                       dg_stream_t stream);
+int dg_wide_linear_dgrad(const float* dy, const float* w, void* dx, int64_t R, int N, int K, int dtype, dg_stream_t stream);
+size_t dg_wide_linear_wgrad_workspace_bytes(int64_t R, int N, int K);
+int dg_wide_linear_wgrad(const float* dy, const void* x, float* dw, float* db, void* workspace, size_t workspace_bytes,
+                         int64_t R, int N, int K, int dtype, dg_stream_t stream);
 
 /* Tail of the Discriminator head (reference models.py:173-178, 207: node_mlp after its first Linear): rows [R,64] of
  * pre-activations z1 -> a1 = act(z1) [R,64], a2 = act(a1 W2^T + b2) [R,32], a3 = act(a2 W3^T + b3) [R,16], out = a3 W4^T + b4
@@ -604,6 +693,27 @@ int dg_embed_node_chain(const float* in, const float* m1, const float* m2, const
 int dg_embed_node_bwd(const float* g, const float* a1, const float* a2, const float* w1, const float* w2, float* g2,
                       float* g1, float* dz, int64_t R, int E, int act, dg_stream_t stream);
 
+/* The same node embedding for node matrices wider than 16 columns, 1 <= E <= 255 (the reference's --features: m_dim = atom
+ * types + 54 descriptor columns; 255 is the resident store's limit on m_dim; csrc/node_wide.hip).  Added after
+ * DG_VERSION 232 without a version bump: the narrow entries above and their limits are unchanged.  Everything is float32 fmaf
+ * arithmetic without atomics: results are bit-identical from run to run.
+ * dg_embed_node_wide_chain has the contract of dg_embed_node_chain (forward with m1 = m2 = NULL for act 0..3; m1 / m2 given: the
+ * masked second-order form, act 0 / 1 only, act 2 / 3: DG_E_ARG), dg_embed_node_wide_bwd that of dg_embed_node_bwd (dz may be
+ * NULL).  Every sum runs bias first, one accumulator per output, inputs in ascending index: for E <= 16 the results equal the
+ * narrow entries' bit for bit.  E outside 1..255: DG_E_SHAPE; R == 0 returns 0 without a launch.                              */
+int dg_embed_node_wide_chain(const float* in, const float* m1, const float* m2, const float* w1, const float* b1,
+                             const float* w2, const float* b2, float* o1, float* o2, int64_t R, int E, int act,
+                             dg_stream_t stream);
+int dg_embed_node_wide_bwd(const float* g, const float* a1, const float* a2, const float* w1, const float* w2, float* g2,
+                           float* g1, float* dz, int64_t R, int E, int act, dg_stream_t stream);
+/* Weight gradient of the first Linear: dw1 [64,E] = g1^T z, db1 [64] = column sums of g1 (db1 may be NULL: the second-order
+ * twin g1^T t has no bias) from g1 [R,64] and z [R,E].  The rows are split over workgroups in a way that depends on R only,
+ * the partial sums go to `workspace` (dg_embed_node_wide_wgrad_workspace_bytes(R, E); 0 for an unsupported shape; a shorter
+ * one: DG_E_WORKSPACE) and are added in a fixed order.  R >= 1, 1 <= E <= 255: others DG_E_SHAPE.                            */
+size_t dg_embed_node_wide_wgrad_workspace_bytes(int64_t R, int E);
+int dg_embed_node_wide_wgrad(const float* g1, const float* z, float* dw1, float* db1, void* workspace, size_t workspace_bytes,
+                             int64_t R, int E, dg_stream_t stream);
+
 /* dg_argmax_decode: reference inference.py:197-198 `torch.max(x, -1)[1]` on logits
  * [rows, E] -> uint8 labels [rows] (first maximum), so only bytes cross PCIe.      */
 int dg_argmax_decode(const float* logits, int64_t rows, int E, unsigned char* out, dg_stream_t stream);
@@ -626,6 +736,38 @@ int dg_argmax_decode(const float* logits, int64_t rows, int E, unsigned char* ou
 int dg_decode_graph(const float* node_logits, const float* edge_logits, const unsigned char* order2, int B, int N, int M,
                     int E, int cap, unsigned char* atoms, unsigned char* bonds, int* n_bonds, unsigned char* component,
                     int* n_components, int* largest, int* largest_size, unsigned short* valence2, dg_stream_t stream);
+
+/* dg_mol_stats: per-molecule statistics of the batch dg_decode_graph wrote (csrc/mol_stats.hip).  Added after
+ * DG_VERSION 232 without a version bump.  Integer arithmetic only: every output is exact and the same from run to run.
+ * dg_mol_stats_workspace_bytes: bytes of dg_mol_stats' workspace for B molecules (their 64-bit keys); 0 for B <= 0.         */
+size_t dg_mol_stats_workspace_bytes(int B);
+/* Statistics of the B molecules dg_decode_graph wrote: atoms [B,N] u8, bonds [B,cap,4] u8, n_bonds / n_components /
+ * largest_size [B] i32, valence2 [B,N] u16 (may be NULL).  Optional: the graph the batch was generated from, in_atoms [B,N] u8
+ * and in_labels [B,N,N] i32 (only i > j is read), and max_valence2 [M] u16, twice the largest allowed valence per atom label
+ * (0xFFFF: no limit; a label >= M has none).
+ *
+ * mol [B,8] i32, one row per molecule; a column is -1 where an input it needs is NULL:
+ *   0 atom_types     distinct values in atoms[b, :]
+ *   1 largest_size, 2 n_components, 3 n_bonds   copied
+ *   4 over_valent    positions with valence2[b,i] > max_valence2[atoms[b,i]]         (needs valence2 and max_valence2)
+ *   5 changed_atoms  positions with atoms[b,i] != in_atoms[b,i]                      (needs in_atoms)
+ *   6 changed_bonds  pairs i > j whose listed bond label (0 when absent from the list) != in_labels[b,i,j]  (needs in_labels)
+ *   7 duplicate_of   smallest j < b with the same atoms row, n_bonds and bond-list dwords; -1: none
+ * A truncated molecule (n_bonds > cap) has changed_bonds = -1 and duplicate_of = -2 and is nobody's duplicate.
+ * tot [16] i64: B; the sums of columns 0..6 over their entries >= 0; molecules with over_valent > 0; with changed_atoms ==
+ * changed_bonds == 0; with duplicate_of == -1; truncated ones; those with n_components == 1; three zeros.
+ *
+ * key_bits in 1..64: a molecule's 64-bit key (an order-free sum of position-dependent mixes of its atoms, n_bonds and bond
+ * rows) is masked to its low key_bits bits; keys only select the pairs that are compared byte by byte, so the result does not
+ * depend on key_bits.  Every element of mol and tot is written by every call; no allocation, no synchronisation.
+ * Null required pointers, bonds == NULL with cap > 0, misaligned bonds (4) / mol (16) / tot, workspace (8), key_bits outside
+ * 1..64: DG_E_ARG; B < 0, N outside 1..256, cap < 0, M outside 1..256 with max_valence2: DG_E_SHAPE; workspace_bytes below
+ * dg_mol_stats_workspace_bytes(B): DG_E_WORKSPACE.  The shape and key_bits are checked first.  B == 0 writes tot (all zeros)
+ * and needs no other pointer.                                                                                               */
+int dg_mol_stats(const unsigned char* atoms, const unsigned char* bonds, const int* n_bonds, const int* n_components,
+                 const int* largest_size, const unsigned short* valence2, const unsigned char* in_atoms, const int* in_labels,
+                 const unsigned short* max_valence2, int B, int N, int cap, int M, int key_bits, int* mol, int64_t* tot,
+                 void* workspace, size_t workspace_bytes, dg_stream_t stream);
 
 /* ---- Tanimoto similarity of bit fingerprints (csrc/fp_tanimoto.hip; reference src/util/utils.py:550-611,
  * average_agg_tanimoto / internal_diversity).  Added after DG_VERSION 232 without a version bump.

@@ -1,4 +1,4 @@
-"""numpy restatement of `dg_mol_stats` (include/druggen_hip_mol_stats.h), written from its specification: every column of
+"""numpy restatement of `dg_mol_stats` (include/druggen_hip.h), written from its specification: every column of
 `mol` and every entry of `tot`, in plain loops over dense label matrices.  No keys: duplicates are a double loop that compares
 the label matrices.  The molecules are the per-molecule dicts of tests/decode_graph_ref.py (`decode_labels`)."""
 import numpy as np

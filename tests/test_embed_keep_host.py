@@ -1,9 +1,5 @@
 """Argument checks of the sign-keeping edge-embedding entries (csrc/embed_sym_keep.hip): they answer before anything touches a
 GPU, so they run everywhere."""
-import os
-import re
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_ARG = -2
 SHAPE = (1, 9, 5, 64, 128)      # B, N, E, H, C
 P = 4096                        # any non-NULL address: refused calls read nothing
@@ -50,28 +46,8 @@ def test_smooth_activations_and_null_signs_are_refused():
     assert b"null pointer" in lib.dg_last_error_string()
 
 
-def test_ctypes_table_matches_the_add_on_header():
-    """include/druggen_hip_embed_keep.h against ``_lib.EMBED_KEEP_SIGNATURES``, parameter by parameter (the check
-    tests/test_host.py makes for druggen_hip.h and ``_lib.SIGNATURES``), and every entry exported by the library."""
-    import ctypes
+def test_entries_are_in_the_ctypes_table():
+    """tests/test_host.py holds every row of the table against include/druggen_hip.h."""
     from druggen_amd import _lib
-    header = open(os.path.join(ROOT, "include", "druggen_hip_embed_keep.h")).read()
-    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
-    header = re.sub(r"^\s*#.*$", " ", header, flags=re.M)
-    protos = re.findall(r"([A-Za-z_][\w\s\*]*?)\b(dg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", header)
-    assert len(protos) == 4
-    assert {name for _, name, _ in protos} == set(_lib.EMBED_KEEP_SIGNATURES)
-    assert not set(_lib.EMBED_KEEP_SIGNATURES) & set(_lib.SIGNATURES)
-
-    def kind(decl):
-        decl = re.sub(r"\bconst\b", " ", decl).strip()
-        if "*" in decl or re.match(r"dg_stream_t\b", decl):
-            return "pointer"
-        return decl.split()[0]
-
-    named = {ctypes.c_int: "int", ctypes.c_size_t: "size_t", ctypes.c_void_p: "pointer"}
-    lib = _lib.load()
-    for ret, name, params in protos:
-        res, args = _lib.EMBED_KEEP_SIGNATURES[name]
-        assert [kind(ret)] + [kind(p) for p in params.split(",")] == [named[res]] + [named[a] for a in args], name
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == args
+    assert {"dg_embed_sym_sign_words", "dg_embed_sym_fwd_keep", "dg_embed_sym_bwd_keep",
+            "dg_embed_sym_bwd2_keep"} <= set(_lib.SIGNATURES)

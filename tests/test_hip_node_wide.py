@@ -1,4 +1,4 @@
-"""The node-side layers of a --features model on their HIP kernels (csrc/node_wide.hip, include/druggen_hip_node_wide.h,
+"""The node-side layers of a --features model on their HIP kernels (csrc/node_wide.hip, include/druggen_hip.h,
 functional/heads.py): the node embedding chain for input widths 17..255 in every order the narrow chain serves, its first
 Linear's weight gradient, and the node readout for 17..255 classes -- against the narrow kernels bit for bit where both run,
 against float64 on the CPU elsewhere, through the autograd nodes and through one whole GAN step."""

@@ -60,15 +60,22 @@ def _header_kind(decl):
 
 def test_ctypes_table_matches_header_parameter_by_parameter():
     """Every prototype of the header against ``_lib.SIGNATURES``: return type, parameter count and each parameter's kind in
-    order -- a row that is one ``int64_t`` off would pass the name check above and corrupt memory on the GPU."""
+    order -- a row that is one ``int64_t`` off would pass the name check above and corrupt memory on the GPU -- and the
+    loaded functions typed from that table.  This is the only place the header is parsed: a dict literal silently keeps the
+    last of two equal keys, so the counts and the uniqueness of the names stand for every pairwise disjointness check."""
     from druggen_amd import _lib
     header = open(os.path.join(ROOT, "include", "druggen_hip.h")).read()
     header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
     header = re.sub(r"//[^\n]*", " ", header)
     header = re.sub(r"^\s*#.*$", " ", header, flags=re.M)
     protos = re.findall(r"([A-Za-z_][\w\s\*]*?)\b(dg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", header)
-    assert len(protos) == 93, len(protos)
-    assert {name for _, name, _ in protos} == set(_lib.SIGNATURES)
+    assert len(protos) == 112, len(protos)
+    names = [name for _, name, _ in protos]
+    assert len(set(names)) == len(names), sorted(n for n in set(names) if names.count(n) > 1)
+    assert len(_lib.SIGNATURES) == 112, len(_lib.SIGNATURES)
+    assert set(names) == set(_lib.SIGNATURES)
+    assert names == list(_lib.SIGNATURES)            # the table is kept in the header's order
+    lib = _lib.load()
     wrong = []
     for ret, name, params in protos:
         res, args = _lib.SIGNATURES[name]
@@ -77,7 +84,24 @@ def test_ctypes_table_matches_header_parameter_by_parameter():
         got = [_ctypes_kind(res)] + [_ctypes_kind(a) for a in args]
         if want != got:
             wrong.append((name, want, got))
+        fn = getattr(lib, name)
+        assert fn.argtypes == args and fn.restype == res, name
     assert not wrong, wrong
+
+
+def test_lib_constants_match_header():
+    """The constants ``_lib.py`` mirrors by hand: the profiler's kernel ids, the dtype codes and the edge-row default."""
+    from druggen_amd import _lib
+    header = open(os.path.join(ROOT, "include", "druggen_hip.h")).read()
+    fold = lambda s: s.replace("_", "").lower()
+    ids = {fold(k): int(v) for k, v in re.findall(r"\bDG_K_([A-Z0-9_]+)\s*=\s*(\d+)", header) if k != "COUNT"}
+    assert len(ids) == len(_lib.KERNEL_IDS) and ids == {fold(k): v for k, v in _lib.KERNEL_IDS.items()}
+    macro = {k: int(v) for k, v in re.findall(r"^#define\s+(DG_[A-Z0-9_]+)\s+\(?(-?\d+)\)?", header, flags=re.M)}
+    assert _lib.DTYPES == {torch.float32: macro["DG_DTYPE_F32"], torch.bfloat16: macro["DG_DTYPE_BF16"]}
+    for name in ("F32_H16", "F32_H24", "F32_DH16", "F32_DH24", "F32_H32", "F32_H32_DH16"):
+        assert getattr(_lib, name) == macro["DG_DTYPE_" + name], name
+    assert len({macro[k] for k in macro if k.startswith("DG_DTYPE_")}) == 8          # eight codes, all distinct
+    assert _lib.EDGE_ROWS == macro["DG_EDGE_ROWS"]
 
 
 def test_argument_validation_needs_no_gpu():

@@ -1,48 +1,23 @@
-"""Host side of the wide node layers (include/druggen_hip_node_wide.h, csrc/node_wide.hip): the add-on header against its ctypes
-table, the exports, and every argument check -- all of which return before a launch.  No GPU."""
+"""Host side of the wide node layers (csrc/node_wide.hip): their rows of the ctypes table and every argument check -- all of
+which return before a launch.  No GPU.  tests/test_host.py holds the table against include/druggen_hip.h."""
 import ctypes
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPE, ARG, WORKSPACE = -1, -2, -3      # DG_E_SHAPE, DG_E_ARG, DG_E_WORKSPACE of include/druggen_hip.h
 ENTRIES = {"dg_embed_node_wide_chain", "dg_embed_node_wide_bwd", "dg_embed_node_wide_wgrad_workspace_bytes",
            "dg_embed_node_wide_wgrad", "dg_wide_linear_fwd", "dg_wide_linear_dgrad", "dg_wide_linear_wgrad_workspace_bytes",
            "dg_wide_linear_wgrad"}
 
 
-def test_ctypes_table_matches_the_add_on_header():
-    """Parameter by parameter, as tests/test_resident_features_host.py does for its header; disjoint from the other tables;
-    exported by the library."""
+def test_wide_entries_take_the_narrow_parameter_lists():
+    """The contracts the wide entries take over: same parameter lists as the narrow ones."""
     from druggen_amd import _lib
-    header = open(os.path.join(ROOT, "include", "druggen_hip_node_wide.h")).read()
-    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
-    header = re.sub(r"^\s*#.*$", " ", header, flags=re.M)
-    protos = re.findall(r"([A-Za-z_][\w\s\*]*?)\b(dg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", header)
-    assert len(protos) == len(ENTRIES)
-    assert {name for _, name, _ in protos} == set(_lib.NODE_WIDE_SIGNATURES) == ENTRIES
-    for other in (_lib.SIGNATURES, _lib.EMBED_KEEP_SIGNATURES, _lib.EMBED_SMOOTH_SIGNATURES, _lib.MOL_FEATURES_SIGNATURES):
-        assert not set(_lib.NODE_WIDE_SIGNATURES) & set(other)
-
-    def kind(decl):
-        decl = re.sub(r"\bconst\b", " ", decl).strip()
-        if "*" in decl or re.match(r"dg_stream_t\b", decl):
-            return "pointer"
-        return decl.split()[0]
-
-    named = {ctypes.c_int: "int", ctypes.c_int64: "int64_t", ctypes.c_void_p: "pointer", ctypes.c_size_t: "size_t"}
-    lib = _lib.load()
-    for ret, name, params in protos:
-        res, args = _lib.NODE_WIDE_SIGNATURES[name]
-        assert [kind(ret)] + [kind(p) for p in params.split(",")] == [named[res]] + [named[a] for a in args], name
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == args and getattr(lib, name).restype == res
-    # the contracts the wide entries take over: same parameter lists as the narrow ones
+    assert ENTRIES <= set(_lib.SIGNATURES)
     for wide, narrow in (("dg_embed_node_wide_chain", "dg_embed_node_chain"), ("dg_embed_node_wide_bwd", "dg_embed_node_bwd"),
                          ("dg_wide_linear_fwd", "dg_skinny_linear_fwd"), ("dg_wide_linear_dgrad", "dg_skinny_linear_dgrad"),
                          ("dg_wide_linear_wgrad", "dg_skinny_linear_wgrad")):
-        assert _lib.NODE_WIDE_SIGNATURES[wide] == _lib.SIGNATURES[narrow]
+        assert _lib.SIGNATURES[wide] == _lib.SIGNATURES[narrow]
 
 
 @pytest.fixture(scope="module")

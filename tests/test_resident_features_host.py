@@ -1,10 +1,8 @@
 """Host side of the feature plane of the GPU-resident molecule set (druggen_amd/resident.py, `pack_features`): node matrices
 that are a one-hot atom type followed by F columns of 0 / 1 (the reference's --features) are split at `atom_dim` into today's
 `atoms` byte and a bit plane, and a numpy unpack written here gives every `x` back exactly; the refusals; the default `pack`
-as it was; the add-on header against its ctypes table; the argument checks of `dg_mol_gather_features`.  No GPU."""
+as it was; the ctypes row of `dg_mol_gather_features` against `dg_mol_gather`'s, and its argument checks.  No GPU."""
 import ctypes
-import os
-import re
 from types import SimpleNamespace
 
 import numpy as np
@@ -12,7 +10,6 @@ import pytest
 
 from druggen_amd.resident import ResidentMolecules
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BLOCKS = (5, 9, 6, 9, 1, 1, 5, 5, 5, 1, 7)      # the reference's descriptor blocks (dataset.py:161-185): 54 columns
 N, ATOM_DIM, N_MOL = 6, 9, 5
 
@@ -149,34 +146,12 @@ def test_default_pack_still_refuses_feature_matrices():
     assert len(ResidentMolecules.pack([good])) == 3
 
 
-def test_ctypes_table_matches_the_add_on_header():
-    """include/druggen_hip_mol_features.h against ``_lib.MOL_FEATURES_SIGNATURES``, parameter by parameter (as
-    tests/test_embed_keep_host.py does for its header), disjoint from the other tables, and exported by the library."""
+def test_gather_features_extends_the_parameter_list_of_gather():
+    """dg_mol_gather's parameters, in its order, with the plane after `entries` and (W, atom_dim) after E (tests/test_host.py
+    holds both rows against include/druggen_hip.h)."""
     from druggen_amd import _lib
-    header = open(os.path.join(ROOT, "include", "druggen_hip_mol_features.h")).read()
-    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
-    header = re.sub(r"^\s*#.*$", " ", header, flags=re.M)
-    protos = re.findall(r"([A-Za-z_][\w\s\*]*?)\b(dg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", header)
-    assert len(protos) == 1
-    assert {name for _, name, _ in protos} == set(_lib.MOL_FEATURES_SIGNATURES) == {"dg_mol_gather_features"}
-    for other in (_lib.SIGNATURES, _lib.EMBED_KEEP_SIGNATURES, _lib.EMBED_SMOOTH_SIGNATURES):
-        assert not set(_lib.MOL_FEATURES_SIGNATURES) & set(other)
-
-    def kind(decl):
-        decl = re.sub(r"\bconst\b", " ", decl).strip()
-        if "*" in decl or re.match(r"dg_stream_t\b", decl):
-            return "pointer"
-        return decl.split()[0]
-
-    named = {ctypes.c_int: "int", ctypes.c_int64: "int64_t", ctypes.c_void_p: "pointer"}
-    lib = _lib.load()
-    for ret, name, params in protos:
-        res, args = _lib.MOL_FEATURES_SIGNATURES[name]
-        assert [kind(ret)] + [kind(p) for p in params.split(",")] == [named[res]] + [named[a] for a in args], name
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == args
-    # dg_mol_gather's parameters, in its order, with the plane after `entries` and (W, atom_dim) after E
     base = list(_lib.SIGNATURES["dg_mol_gather"][1])
-    assert _lib.MOL_FEATURES_SIGNATURES["dg_mol_gather_features"][1] == base[:3] + [ctypes.c_void_p] + base[3:9] + [ctypes.c_int] * 2 + base[9:]
+    assert _lib.SIGNATURES["dg_mol_gather_features"][1] == base[:3] + [ctypes.c_void_p] + base[3:9] + [ctypes.c_int] * 2 + base[9:]
 
 
 def test_argument_validation_needs_no_gpu():

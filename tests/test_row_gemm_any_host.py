@@ -1,42 +1,16 @@
-"""Host side of the any-width row GEMM (include/druggen_hip_row_gemm_any.h, csrc/row_gemm_any.hip): the add-on header against its
-ctypes table, the exports, the packed size and every argument check -- all of which return before a launch.  No GPU."""
+"""Host side of the any-width row GEMM (csrc/row_gemm_any.hip): its rows of the ctypes table, the packed size and every argument
+check -- all of which return before a launch.  No GPU.  tests/test_host.py holds the table against include/druggen_hip.h."""
 import ctypes
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPE, ARG = -1, -2      # DG_E_SHAPE, DG_E_ARG of include/druggen_hip.h
 ENTRIES = {"dg_row_gemm_any_packed_bytes", "dg_row_gemm_any_pack", "dg_row_gemm_any"}
 
 
-def test_ctypes_table_matches_the_add_on_header():
-    """Parameter by parameter, as tests/test_node_wide_host.py does for its header; disjoint from the other tables; exported by
-    the library."""
+def test_entries_are_in_the_ctypes_table():
     from druggen_amd import _lib
-    header = open(os.path.join(ROOT, "include", "druggen_hip_row_gemm_any.h")).read()
-    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
-    header = re.sub(r"^\s*#.*$", " ", header, flags=re.M)
-    protos = re.findall(r"([A-Za-z_][\w\s\*]*?)\b(dg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", header)
-    assert len(protos) == len(ENTRIES)
-    assert {name for _, name, _ in protos} == set(_lib.ROW_GEMM_ANY_SIGNATURES) == ENTRIES
-    for other in (_lib.SIGNATURES, _lib.EMBED_KEEP_SIGNATURES, _lib.EMBED_SMOOTH_SIGNATURES, _lib.MOL_FEATURES_SIGNATURES,
-                  _lib.NODE_WIDE_SIGNATURES):
-        assert not set(_lib.ROW_GEMM_ANY_SIGNATURES) & set(other)
-
-    def kind(decl):
-        decl = re.sub(r"\bconst\b", " ", decl).strip()
-        if "*" in decl or re.match(r"dg_stream_t\b", decl):
-            return "pointer"
-        return decl.split()[0]
-
-    named = {ctypes.c_int: "int", ctypes.c_int64: "int64_t", ctypes.c_void_p: "pointer", ctypes.c_size_t: "size_t"}
-    lib = _lib.load()
-    for ret, name, params in protos:
-        res, args = _lib.ROW_GEMM_ANY_SIGNATURES[name]
-        assert [kind(ret)] + [kind(p) for p in params.split(",")] == [named[res]] + [named[a] for a in args], name
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == args and getattr(lib, name).restype == res
+    assert ENTRIES <= set(_lib.SIGNATURES)
 
 
 @pytest.fixture(scope="module")
