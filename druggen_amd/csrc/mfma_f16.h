@@ -28,5 +28,10 @@ __device__ __forceinline__ void mfma16_first(f32x4& acc, const f16x8& a, const f
 }
 // in front of the first vector read of a chain's results
 __device__ __forceinline__ void mfma_results_ready() { asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); }
+// the same fence in the middle of an MFMA stream, for three finished chains only: tied to their accumulators, so that no
+// vector read of them is moved in front of it while the MFMAs of other chains go on behind it
+__device__ __forceinline__ void mfma_results_ready(f32x4& a0, f32x4& a1, f32x4& a2) {
+    asm volatile("s_nop 15\n\ts_nop 15" : "+v"(a0), "+v"(a1), "+v"(a2)::"memory");
+}
 
 }  // namespace dg

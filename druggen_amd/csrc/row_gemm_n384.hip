@@ -15,8 +15,9 @@
 //   waves 0..7   consumers: wave w owns output channels [48 w, 48 w + 48) with its weight fragments resident (96
 //                VGPRs, gathered once from the packed weight).  Swapped product on v_mfma_f32_16x16x32_f16 (weights =
 //                A operand, activations = B operand): a lane ends up with 4 consecutive channels of ONE row.  Per
-//                32-row stage: 16 ds_read_b128, 72 MFMAs, then scale + bias + ReLU (+ bit masks) and one 16-byte LDS
-//                write per block into the output tile.  No global memory operation at all: the ReLU mask words travel
+//                32-row stage: 16 ds_read_b128, 72 MFMAs in two passes (rows 0..15, then rows 16..31), scale + bias +
+//                ReLU (+ bit masks) and one 16-byte LDS write per block into the output tile -- for the first pass's
+//                rows between the MFMAs of the second.  No global memory operation at all: the ReLU mask words travel
 //                through LDS too (a consumer that stored its own word waited for that store, vmcnt(0), every stage).
 //   one s_barrier per stage; planes and output tile double-buffered.
 //
@@ -33,9 +34,6 @@
 #include "pair.h"
 #include "traversal.h"
 
-#ifndef N3_SCHED
-#define N3_SCHED 1    // consumers: fragment reads one k-step ahead, per row block (0: hipcc's order, A/B builds)
-#endif
 #ifndef N3_DBG
 #define N3_DBG 0      // ablation builds (scripts/build_variant.sh, scripts/n384_variants.sh): 1 no MFMAs, 2 no epilogue arithmetic
 #endif                // (raw accumulators to the tile), 4 no output stores, 8 no global fetch of A
@@ -313,11 +311,20 @@ __global__ __launch_bounds__(64 * (kCons + kProd)) void row_gemm_n384_kernel(con
             const u32x2 bw = *reinterpret_cast<const u32x2*>(smem + kOffBitsOut + (tc & 1) * 2048 + pt * 8);
             __builtin_amdgcn_raw_buffer_store_b64(bw, rbits, static_cast<unsigned>(pt) * 8u, 0, 0);
         };
+        // The prologue issues the vector memory operations of a steady-state iteration: a store_out(-1) (every store dropped:
+        // zero-sized ranges) behind each fetch, as in the loop.  split() waits for its loads with a COUNTED vmcnt, and hipcc
+        // takes the count of a wait inside the loop as the minimum over the ways into it: with a prologue of fetches only, the
+        // second and third split of an iteration waited at vmcnt(28) and (42) of the 52 operations issued behind their loads
+        // (H32) -- for the stores of the last stage but one to be acknowledged, a stall of the producers on the write path in
+        // every stage.  With this prologue all three wait at 52 (<1,2,2>: at 34, where they waited at 18 and 26).
         fetch(pf[0], mk[0], 0);
         fetch(pf[1], mk[1], 1);
+        store_out(-1);
         fetch(pf[2], mk[2], 2);
+        store_out(-1);
         split(pf[0], mk[0], 0);
         fetch(pf[0], mk[0], 3);
+        store_out(-1);
         __syncthreads();
         for (int t = 0; t < TP; t += 3) {
             // iteration t: the consumers are on stage t; planes of stage t + 1 are written, the output tile of stage t - 1 leaves
@@ -359,93 +366,130 @@ __global__ __launch_bounds__(64 * (kCons + kProd)) void row_gemm_n384_kernel(con
     const unsigned relu_sel = ep.relu ? 0xFFFFFFFFu : 0u;
     __builtin_amdgcn_s_waitcnt(0x0F70);      // weight fragments are in registers
     __syncthreads();                         // stage 0 is in planes[0], the tables are written
+    // A lane's channels never change: where the register budget allows -- the two- and one-product instances, which keep no
+    // lo fragments -- the inverse column scales stay in registers instead of 3 ld4 per stage (the three-product instances sit
+    // at 166 of 168 VGPRs).
+    constexpr bool HOIST = MODE == 2 && NP != 3;
+    float4 csh[3];
+    if (HOIST) {
+#pragma unroll
+        for (int cb = 0; cb < 3; ++cb) csh[cb] = ld4(tab + 48 * w + 16 * cb + 4 * kq);
+    }
     for (int t = 0; t < TP; ++t) {
         if (t < T) {
             const char* pl = smem + (t & 1) * kStage;
             const unsigned bits = *reinterpret_cast<const unsigned*>(smem + kOffBitsIn + (t & 1) * 2048 + (w * 64 + lane) * 4);
+            char* ot = smem + kOffOut + (t & 1) * kOut;
+            // A stage is two passes, one per 16-row block rb, of four k-steps each: pass q >> 2, k-step q & 3, q = 0 .. 7.  Every
+            // accumulator still sees its products in the order (k-step, term) -- the results are bit-identical to the order
+            // "k-step outside, row block inside" -- but the accumulators of row block 0 are finished after HALF of the stage's
+            // MFMAs, and their epilogue (scale, bias, ReLU / mask, tile write) is issued in slices between the MFMA groups of
+            // row block 1: the two consumer waves of a SIMD run in lock step (one barrier per stage), so vector work that only
+            // starts behind the last MFMA finds the matrix pipe idle in both of them.  Only row block 1's epilogue is left there.
             f32x4 acc[2][3];
-            // Fragment reads run one k-step AHEAD, per row block: the fragments of (k-step ks + 1, row block rb) are requested
-            // right behind the MFMAs of (ks, rb) -- into the same registers, the MFMAs have read them at issue -- and arrive
-            // while the other row block's MFMAs run.  (hipcc's own order was 4 reads, wait, 18 MFMAs, 4 reads, wait ...: every
-            // k-step exposed one LDS round trip with the matrix pipe idle; N3_SCHED=0 keeps that order for A/B builds.)
+            // fragment reads run one k-step AHEAD: those of q + 1 are requested in front of the MFMAs of q, into the registers
+            // of q - 1 (whose MFMAs have read them at issue), and arrive while the MFMAs of q run.
             f16x8 xh[2], xl[2];
-            auto read_frags = [&](int ks, int rb) {
+            auto read_frags = [&](int q) {
+                const int ks = q & 3, rb = q >> 2;
                 const char* p0 = pl + ks * 2048 + rb * 256 + ((ks & 1) ? xo_o : xo_e);
-                xh[rb] = *reinterpret_cast<const f16x8*>(p0);
-                if (NP == 3) xl[rb] = *reinterpret_cast<const f16x8*>(p0 + kPlane);
+                xh[q & 1] = *reinterpret_cast<const f16x8*>(p0);
+                if (NP == 3) xl[q & 1] = *reinterpret_cast<const f16x8*>(p0 + kPlane);
             };
-            read_frags(0, 0);
-            read_frags(0, 1);
+            // one MFMA group: product ti of step q over the wave's three channel blocks.  w_lo.x_hi, w_hi.x_lo, w_hi.x_hi:
+            // smallest terms first; three accumulators in rotation
+            constexpr int NT = NP;      // groups per k-step
+            auto products = [&](int q, int ti) {
+                const int ks = q & 3, rb = q >> 2, s = q & 1;
+                const int term = NP == 3 ? ti : (NP == 2 ? 2 * ti : 2);
+                constexpr int LO = NP == 1 ? 0 : 1;      // (index of the weights' lo plane; never read when NP == 1)
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
+                for (int cb = 0; cb < 3; ++cb) {
+                    if (N3_DBG & 1) {
+                        if (ks == 0 && ti == 0) acc[rb][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+                        acc[rb][cb][0] += static_cast<float>(xh[s][0]) * static_cast<float>(wf[cb][ks][0][0]);
+                    } else if (ks == 0 && ti == 0) mfma16_first(acc[rb][cb], wf[cb][ks][term == 0 ? LO : 0], xh[s]);
+                    else mfma16(acc[rb][cb], wf[cb][ks][term == 0 ? LO : 0], term == 1 ? xl[s] : xh[s]);
+                }
+            };
+            // epilogue: lane (row n of block rb, channel group kq) holds channels 48 w + 16 cb + 4 kq + i of its row
+            unsigned newbits = 0;
+            float rs[2];
+            float4 cs[3], bs[3];
+            auto epi_load = [&](int rb, int cb) {      // inverse row scale, inverse column scales and bias of one block
+                if (cb == 0) rs[rb] = *reinterpret_cast<const float*>(pl + 2 * kPlane + (16 * rb + n) * 4);
+                const int c0 = 48 * w + 16 * cb + 4 * kq;
+                cs[cb] = HOIST ? csh[cb] : ld4(tab + c0);
+                bs[cb] = MODE == 2 ? make_float4(0.f, 0.f, 0.f, 0.f) : ld4(tab + 384 + c0);      // (MODE 2 has no bias: the table holds zeros)
+            };
+            auto epi_block = [&](int rb, int cb) {
+                const int row = 16 * rb + n;
+                const int c0 = 48 * w + 16 * cb + 4 * kq;
+                const int slot = (c0 >> 2) ^ (row & 7);
+                if (N3_DBG & 2) {
+                    *reinterpret_cast<float4*>(ot + row * 1536 + slot * 16) =
+                        make_float4(acc[rb][cb][0], acc[rb][cb][1], acc[rb][cb][2], acc[rb][cb][3]);
+                    return;
+                }
+                const float r = rs[rb];
+                float v[4] = {fmaf(acc[rb][cb][0], r * cs[cb].x, bs[cb].x), fmaf(acc[rb][cb][1], r * cs[cb].y, bs[cb].y),
+                              fmaf(acc[rb][cb][2], r * cs[cb].z, bs[cb].z), fmaf(acc[rb][cb][3], r * cs[cb].w, bs[cb].w)};
 #pragma unroll
-                for (int rb = 0; rb < 2; ++rb) {
-                    // w_lo.x_hi, w_hi.x_lo, w_hi.x_hi: smallest terms first; three accumulators in rotation
-#pragma unroll
-                    for (int term = (NP == 1 ? 2 : 0); term < 3; ++term)
-#pragma unroll
-                        for (int cb = 0; cb < 3; ++cb) {
-                            if (NP != 3 && term == 1) continue;
-                            constexpr int LO = NP == 1 ? 0 : 1;      // (index of the weights' lo plane; never read when NP == 1)
-                            constexpr int FIRST = NP == 1 ? 2 : 0;
-                            if (N3_DBG & 1) {
-                                if (ks == 0 && term == FIRST) acc[rb][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-                                acc[rb][cb][0] += static_cast<float>(xh[rb][0]) * static_cast<float>(wf[cb][ks][0][0]);
-                            } else if (ks == 0 && term == FIRST) mfma16_first(acc[rb][cb], wf[cb][ks][term == 0 ? LO : 0], xh[rb]);
-                            else mfma16(acc[rb][cb], wf[cb][ks][term == 0 ? LO : 0], term == 1 ? xl[rb] : xh[rb]);
-                        }
-#if N3_SCHED
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (ks < 3) read_frags(ks + 1, rb);
-                    __builtin_amdgcn_sched_barrier(0);
-#else
-                    if (ks < 3 && rb == 1) {
-                        read_frags(ks + 1, 0);
-                        read_frags(ks + 1, 1);
+                for (int i = 0; i < 4; ++i) {
+                    const int bit = (rb * 3 + cb) * 4 + i;
+                    if (MODE == 1) {
+                        newbits |= v[i] > 0.f ? (1u << bit) : 0u;
+                        v[i] = fmaxf(v[i], 0.f);
+                    } else if (MODE == 2) {
+                        // bit -> 0 / ~0 (one v_bfe_i32), and: no compare, no select
+                        const int keep = __builtin_amdgcn_sbfe(static_cast<int>(bits), bit, 1);
+                        v[i] = __uint_as_float(__float_as_uint(v[i]) & static_cast<unsigned>(keep));
+                    } else {
+                        newbits |= (v[i] > 0.f ? 1u : 0u) << bit;
+                        v[i] = __uint_as_float((__float_as_uint(fmaxf(v[i], 0.f)) & relu_sel) | (__float_as_uint(v[i]) & ~relu_sel));
+                        v[i] = (bits >> bit) & 1u ? v[i] : 0.f;
                     }
-#endif
+                }
+                *reinterpret_cast<float4*>(ot + row * 1536 + slot * 16) = make_float4(v[0], v[1], v[2], v[3]);
+            };
+            // row block 0's epilogue in six slices: loads of block cb (even j), then its arithmetic and tile write (odd j) a slice
+            // later.  (The generic form has no registers left for a load ahead -- 168 VGPRs, one over spilled: it loads in the
+            // slice that computes.)
+            auto epi_slice = [&](int j) {
+                if (MODE == 0 && !(j & 1)) return;
+                if (MODE == 0 || !(j & 1)) epi_load(0, j >> 1);
+                if (j & 1) epi_block(0, j >> 1);
+            };
+            read_frags(0);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                if (q < 7) read_frags(q + 1);
+                __builtin_amdgcn_sched_barrier(0);      // (sched barriers: the slices stay where they are written)
+#pragma unroll
+                for (int ti = 0; ti < NT; ++ti) {
+                    products(q, ti);
+                    if (q >= 4) {
+                        // g: MFMA group of the second pass, 0 .. 4 NT - 1.  Behind its first k-step (NT groups after row block
+                        // 0's last MFMA) the fence of mfma_results_ready(), tied to row block 0's accumulators so that no read
+                        // of them is moved in front of it; then one slice behind each of the 3 NT groups that follow: slice j
+                        // behind group NT + j (NT = 2), NT + j / 2 (NT = 1), NT + 0, 2, 3, 5, 6, 8 (NT = 3).
+                        const int g = (q - 4) * NT + ti;
+                        if (g == NT - 1) mfma_results_ready(acc[0][0], acc[0][1], acc[0][2]);
+                        if (g >= NT) {
+#pragma unroll
+                            for (int j = 0; j < 6; ++j)
+                                if ((NT == 3 ? 3 * (j >> 1) + 2 * (j & 1) : j * NT / 2) == g - NT) epi_slice(j);
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
                 }
             }
             mfma_results_ready();
-            // epilogue: lane (row n of block rb, channel group kq) holds channels 48 w + 16 cb + 4 kq + i of its row
-            char* ot = smem + kOffOut + (t & 1) * kOut;
-            unsigned newbits = 0;
 #pragma unroll
-            for (int rb = 0; rb < 2; ++rb) {
-                const int row = 16 * rb + n;
-                const float rs = *reinterpret_cast<const float*>(pl + 2 * kPlane + row * 4);
+            for (int cb = 0; cb < 3; ++cb) epi_load(1, cb);
 #pragma unroll
-                for (int cb = 0; cb < 3; ++cb) {
-                    const int c0 = 48 * w + 16 * cb + 4 * kq;
-                    const float4 cs = ld4(tab + c0), bs = ld4(tab + 384 + c0);
-                    if (N3_DBG & 2) {
-                        const int slot = (c0 >> 2) ^ (row & 7);
-                        *reinterpret_cast<float4*>(ot + row * 1536 + slot * 16) =
-                            make_float4(acc[rb][cb][0], acc[rb][cb][1], acc[rb][cb][2], acc[rb][cb][3]);
-                        continue;
-                    }
-                    float v[4] = {fmaf(acc[rb][cb][0], rs * cs.x, bs.x), fmaf(acc[rb][cb][1], rs * cs.y, bs.y),
-                                  fmaf(acc[rb][cb][2], rs * cs.z, bs.z), fmaf(acc[rb][cb][3], rs * cs.w, bs.w)};
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const int bit = (rb * 3 + cb) * 4 + i;
-                        if (MODE == 1) {
-                            newbits |= v[i] > 0.f ? (1u << bit) : 0u;
-                            v[i] = fmaxf(v[i], 0.f);
-                        } else if (MODE == 2) {
-                            // bit -> 0 / ~0 (one v_bfe_i32), and: no compare, no select
-                            const int keep = __builtin_amdgcn_sbfe(static_cast<int>(bits), bit, 1);
-                            v[i] = __uint_as_float(__float_as_uint(v[i]) & static_cast<unsigned>(keep));
-                        } else {
-                            newbits |= (v[i] > 0.f ? 1u : 0u) << bit;
-                            v[i] = __uint_as_float((__float_as_uint(fmaxf(v[i], 0.f)) & relu_sel) | (__float_as_uint(v[i]) & ~relu_sel));
-                            v[i] = (bits >> bit) & 1u ? v[i] : 0.f;
-                        }
-                    }
-                    const int slot = (c0 >> 2) ^ (row & 7);
-                    *reinterpret_cast<float4*>(ot + row * 1536 + slot * 16) = make_float4(v[0], v[1], v[2], v[3]);
-                }
-            }
+            for (int cb = 0; cb < 3; ++cb) epi_block(1, cb);
             *reinterpret_cast<unsigned*>(smem + kOffBitsOut + (t & 1) * 2048 + (w * 64 + lane) * 4) = newbits;
         }
         __syncthreads();
