@@ -11,6 +11,7 @@
 //   mol_stats_totals one workgroup: tot[16] from mol[B, 8]
 // Every element of mol and tot is stored by every call; the key workspace is rewritten before it is read.
 #include "common.h"
+#include "mol_key.h"
 
 namespace dg {
 namespace {
@@ -19,25 +20,7 @@ constexpr int MST_THREADS = 256;
 constexpr int MST_COLS = 8;
 constexpr int MST_TOT = 16;
 
-// splitmix64's finaliser over (position, value): the key is the SUM of these over all positions modulo 2^64, so lanes hash in
-// parallel and the order in which they add does not matter.  Positions: atom i -> i, n_bonds -> 256, bond row k -> 257 + k.
-__device__ __forceinline__ unsigned long long mix(unsigned pos, unsigned value) {
-    unsigned long long z = ((static_cast<unsigned long long>(pos) + 1ull) << 32 | value) + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ int wave_sum(int x) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-    return x;
-}
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long x) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-    return x;
-}
+// Key positions (mix of mol_key.h): atom i -> i, n_bonds -> 256, bond row k -> 257 + k.
 
 __global__ __launch_bounds__(MST_THREADS) void mol_stats_rows(
     const unsigned char* __restrict__ atoms, const unsigned* __restrict__ bonds, const int* __restrict__ n_bonds,
@@ -123,16 +106,7 @@ __global__ __launch_bounds__(MST_THREADS) void mol_stats_rows(
 // (called in wave-uniform control flow; the answer is wave-uniform)
 __device__ __forceinline__ bool same_graph(const unsigned char* __restrict__ atoms, const unsigned* __restrict__ bonds, int N,
                                            int cap, int nb, int64_t b, int64_t j, int lane) {
-    const unsigned char *pa = atoms + b * N, *qa = atoms + j * N;
-    bool differ = false;
-    for (int i = lane; i < N; i += 64) differ |= pa[i] != qa[i];
-    if (__any(differ)) return false;
-    const unsigned *pb = bonds + b * cap, *qb = bonds + j * cap;
-    for (int k0 = 0; k0 < nb; k0 += 64) {
-        const int k = k0 + lane;
-        if (__any(k < nb && pb[k] != qb[k])) return false;
-    }
-    return true;
+    return same_rows(atoms + b * N, atoms + j * N, N, bonds + b * cap, bonds + j * cap, nb, lane);
 }
 
 __global__ __launch_bounds__(MST_THREADS) void mol_stats_dups(

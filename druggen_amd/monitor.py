@@ -53,7 +53,8 @@ class MolStats:
       atoms in another order is not recognised.  So ``1 - distinct_fraction`` is a LOWER BOUND on the duplication RDKit's
       ``Uniqueness`` would report, and ``copy_fraction`` is a LOWER BOUND on the share of molecules that are not novel with
       respect to their own input.  Both are alarms for the two failures of this GAN (collapse to a few outputs; the generator
-      returning its input); neither replaces RDKit's Uniqueness or Novelty.
+      returning its input); neither replaces RDKit's Uniqueness or Novelty.  Identity up to the atom order, within the batch
+      and against a stock of molecules, is ``druggen_amd.canon``'s, on the same ``MoleculeBatch``.
 
     ``cpu()`` moves the packed buffer with ONE device->host copy; the fractions read the host copy."""
 
