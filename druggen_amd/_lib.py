@@ -141,6 +141,8 @@ SIGNATURES = {
     "dg_decode_graph": (c_int, [_P] * 3 + [c_int] * 5 + [_P] * 8 + [_P]),
     "dg_mol_stats_workspace_bytes": (c_size_t, [c_int]),
     "dg_mol_stats": (c_int, [_P] * 9 + [c_int] * 5 + [_P, _P, _P, c_size_t, _P]),
+    "dg_mol_canon": (c_int, [_P] * 5 + [c_int] * 4 + [_P] * 8 + [_P]),
+    "dg_mol_canon_match": (c_int, [_P] * 6 + [c_int] * 3 + [_P] * 7 + [c_int] * 3 + [_P, _P] + [_P]),
     "dg_fp_pack": (c_int, [_P, c_int, c_int64, c_int, _P, _P, _P]),
     "dg_fp_tanimoto_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "dg_fp_tanimoto": (c_int, [_P, _P, c_int64, _P, _P, c_int64, c_int, c_int, _P, _P, _P, c_size_t, _P]),

@@ -18,7 +18,6 @@ CSRC = os.path.join(PKG, "csrc")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdruggen_hip.so")
 HEADER = os.path.join(os.path.dirname(PKG), "include", "druggen_hip.h")
-ADDON_HEADERS = [os.path.join(os.path.dirname(PKG), "include", "druggen_hip_canon.h")]
 ARCH = "gfx950"
 
 
@@ -30,7 +29,7 @@ def _stale() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + [HEADER] + ADDON_HEADERS
+    deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + [HEADER]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -42,7 +41,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         raise RuntimeError("hipcc not found: cannot build libdruggen_hip.so")
     os.makedirs(LIB_DIR, exist_ok=True)
     objs, jobs = [], []
-    headers = glob.glob(os.path.join(CSRC, "*.h")) + [HEADER] + ADDON_HEADERS
+    headers = glob.glob(os.path.join(CSRC, "*.h")) + [HEADER]
     for src in sources():
         obj = os.path.join(LIB_DIR, os.path.basename(src) + ".o")
         objs.append(obj)

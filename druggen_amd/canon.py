@@ -3,7 +3,7 @@
 The reference's ``logging()`` (``src/util/utils.py:241-355``) counts distinct canonical SMILES of the longest fragment
 (Uniqueness) and checks them against the input molecules and the drug set (Novelty).  ``monitor.MolStats`` compares decoded graphs
 position by position; here ``canonical_forms`` rewrites every molecule of a device ``decode.MoleculeBatch`` in an atom order that
-depends on the labelled graph alone (``dg_mol_canon``, ``include/druggen_hip_canon.h``), and ``match_forms`` compares those forms
+depends on the labelled graph alone (``dg_mol_canon``, ``include/druggen_hip.h``), and ``match_forms`` compares those forms
 within the batch and against a stock -- the input batch, a drug store, a training store (``dg_mol_canon_match``).
 
 Equal forms ARE isomorphic labelled graphs (a form is a complete relabelled graph), so every duplicate and every stock hit is
@@ -13,62 +13,20 @@ different labelled graphs, so the fractions below bound RDKit's Uniqueness / Nov
 but are not those numbers.  GPU only, no CPU fallback."""
 from __future__ import annotations
 
-from ctypes import c_int, c_void_p
-
-import numpy as np
 import torch
 
 from . import _lib
-from .decode import MoleculeBatch, decode_molecule_graphs
+from ._packed import PackedRecord, check_key_bits as _check_key_bits
+from .decode import decode_molecule_graphs, device_batch
 
 __all__ = ["canonical_forms", "match_forms", "uniqueness_novelty", "CanonicalForms", "CanonicalSet", "FormMatches", "SCOPES",
-           "TOT_FIELDS", "CANON_SIGNATURES"]
+           "TOT_FIELDS"]
 
-_P = c_void_p
-# name -> (restype, argtypes); mirrors include/druggen_hip_canon.h one to one (to be folded into _lib.SIGNATURES with the header)
-CANON_SIGNATURES = {
-    "dg_mol_canon": (c_int, [_P] * 5 + [c_int] * 4 + [_P] * 8 + [_P]),
-    "dg_mol_canon_match": (c_int, [_P] * 6 + [c_int] * 3 + [_P] * 7 + [c_int] * 3 + [_P, _P] + [_P]),
-}
 SCOPES = {"whole": 0, "largest": 1}      # DG_CANON_WHOLE / DG_CANON_LARGEST
 TOT_FIELDS = ("B", "n_distinct", "n_in_stock", "n_novel", "n_truncated", "n_unsplit")
-_TOT_BYTES = 8 * 8
-
-_typed = None
 
 
-def _typed_lib():
-    """The handle of ``_lib.load()`` with the two add-on entries typed (once; AttributeError if the library lacks them)."""
-    global _typed
-    if _typed is None:
-        lib = _lib.load()
-        for name, (res, args) in CANON_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-        _typed = lib
-    return _typed
-
-
-_FIELDS = (("n_atoms", 4), ("n_bonds", 4), ("n_splits", 4), ("n_rounds", 4), ("key", 8), ("order", 1), ("canon_atoms", 1),
-           ("canon_bonds", 1))
-_TORCH_TYPES = {1: torch.uint8, 4: torch.int32, 8: torch.int64}
-_NUMPY_TYPES = {1: np.uint8, 4: np.int32, 8: np.int64}
-
-
-def _layout(B, N, cap):
-    """name -> (byte offset, bytes, element bytes, shape) of the packed buffer, and its size; every field starts on a 16-byte
-    boundary (``decode._layout``'s rule)."""
-    shapes = {"order": (B, N), "canon_atoms": (B, N), "canon_bonds": (B, cap, 4)}
-    table, off = {}, 0
-    for name, item in _FIELDS:
-        shape = shapes.get(name, (B,))
-        nbytes = item * int(np.prod(shape, dtype=np.int64))
-        table[name] = (off, nbytes, item, shape)
-        off += (nbytes + 15) & ~15
-    return table, max(off, 16)
-
-
-class CanonicalForms:
+class CanonicalForms(PackedRecord):
     """The forms of one batch: typed views of one packed byte buffer.
 
     ===============  ===============  ===============================================================================
@@ -86,44 +44,30 @@ class CanonicalForms:
     ``cpu()`` moves the packed buffer with ONE device->host copy; ``form(b)`` reads the host copy."""
 
     def __init__(self, buffer, B, N, cap, scope):
-        self.buffer, self.B, self.N, self.cap, self.scope = buffer, B, N, cap, scope
-        self.is_host = isinstance(buffer, np.ndarray)
-        table, total = _layout(B, N, cap)
-        assert buffer.shape[0] == total
-        for name, (off, nbytes, item, shape) in table.items():
-            part = buffer[off:off + nbytes]
-            view = part.view(_NUMPY_TYPES[item]).reshape(shape) if self.is_host else part.view(_TORCH_TYPES[item]).view(shape)
-            setattr(self, name, view)
+        self.B, self.N, self.cap, self.scope = B, N, cap, scope
+        super().__init__(buffer, B, N, cap)
+
+    @staticmethod
+    def _fields(B, N, cap, scope=None):
+        return (("n_atoms", 4, (B,)), ("n_bonds", 4, (B,)), ("n_splits", 4, (B,)), ("n_rounds", 4, (B,)), ("key", 8, (B,)),
+                ("order", 1, (B, N)), ("canon_atoms", 1, (B, N)), ("canon_bonds", 1, (B, cap, 4)))
 
     @staticmethod
     def empty(B, N, cap, device, scope="largest"):
         """Device forms over an uninitialised buffer (``canonical_forms(..., out=)`` fills every element)."""
-        _, total = _layout(B, N, cap)
-        return CanonicalForms(torch.empty(total, dtype=torch.uint8, device=device), B, N, cap, scope)
-
-    def cpu(self):
-        if self.is_host:
-            return self
-        return CanonicalForms(self.buffer.cpu().numpy(), self.B, self.N, self.cap, self.scope)
+        return CanonicalForms._empty(device, B, N, cap, scope)
 
     def form(self, b):
         """``(n_atoms, n_bonds, atom labels, bond rows)`` of molecule ``b`` as plain Python values (host copy only): equal
         exactly when the two molecules are reported as the same.  None for a truncated molecule."""
-        if not self.is_host:
-            raise RuntimeError("CanonicalForms.form reads the host copy: call .cpu() once for the batch first")
+        self._host("form")
         if self.n_splits[b] < 0:
             return None
         n, nb = int(self.n_atoms[b]), int(self.n_bonds[b])
         return n, nb, tuple(self.canon_atoms[b, :n].tolist()), tuple(map(tuple, self.canon_bonds[b, :nb, :3].tolist()))
 
 
-def _device_batch(batch, who):
-    if not isinstance(batch, MoleculeBatch):
-        raise TypeError(f"{who} takes a decode.MoleculeBatch")
-    if batch.is_host or not batch.buffer.is_cuda:
-        raise RuntimeError("druggen_amd.canon runs on the GPU (no CPU fallback): pass the device MoleculeBatch")
-    if not 1 <= batch.N <= 256:
-        raise ValueError(f"{who}: 1 <= N <= 256, got {batch.N}")
+_layout = CanonicalForms.layout      # (B, N, cap) -> (name -> (byte offset, bytes, element bytes, shape), size)
 
 
 def _scope_code(scope):
@@ -138,7 +82,6 @@ def _launch_canon(batch, code, forms, at=0):
     if batch.B == 0:
         return
     cap = batch.cap
-    _typed_lib()
     _lib.launch("dg_mol_canon", batch.buffer,
                 batch.atoms.data_ptr(), batch.bonds.data_ptr() if cap > 0 else None, batch.n_bonds.data_ptr(),
                 batch.component.data_ptr(), batch.largest.data_ptr(), batch.B, batch.N, cap, code,
@@ -154,7 +97,7 @@ def canonical_forms(batch, scope="largest", out=None):
     except isolated pads (label 0 and no bond).  ``out``: a ``CanonicalForms.empty(B, N, cap, device)`` to write into.  One
     launch; every element is written by every call, nothing is allocated with ``out=`` and nothing synchronises, so the call can
     be captured into a hipGraph."""
-    _device_batch(batch, "canonical_forms")
+    device_batch(batch, "canonical_forms", "canon")
     code = _scope_code(scope)
     B, N, cap = batch.B, batch.N, batch.cap
     dev = batch.buffer.device
@@ -166,11 +109,6 @@ def canonical_forms(batch, scope="largest", out=None):
     out.scope = scope
     _launch_canon(batch, code, out)
     return out
-
-
-def _check_key_bits(key_bits):
-    if not isinstance(key_bits, int) or isinstance(key_bits, bool) or not 1 <= key_bits <= 64:
-        raise ValueError(f"key_bits must be an integer in 1..64, got {key_bits!r}")
 
 
 class CanonicalSet:
@@ -215,7 +153,7 @@ class CanonicalSet:
         return cls.from_forms(forms, key_bits)
 
 
-class FormMatches:
+class FormMatches(PackedRecord):
     """What ``match_forms`` found: typed views of one packed byte buffer (``tot`` first, then ``match``).
 
     ``match`` [B,2] int32: ``duplicate_of`` -- smallest ``j < b`` with an equal form, -1 none, -2 truncated -- and ``stock_hit``
@@ -223,23 +161,20 @@ class FormMatches:
     (``TOT_FIELDS``): B, ``n_distinct`` (``duplicate_of == -1``), ``n_in_stock``, ``n_novel`` (``stock_hit == -1``),
     ``n_truncated``, ``n_unsplit`` (``n_splits == 0``), zeros.  The fractions read the host copy (``cpu()``: one transfer)."""
 
+    TOT_FIELDS = TOT_FIELDS
+    _PAD_END = False      # 64 + 8 B bytes: the buffer ends with its last row
+
     def __init__(self, buffer, B):
-        self.buffer, self.B = buffer, B
-        self.is_host = isinstance(buffer, np.ndarray)
-        assert buffer.shape[0] == _TOT_BYTES + 8 * B
-        if self.is_host:
-            self.tot = buffer[:_TOT_BYTES].view(np.int64)
-            self.match = buffer[_TOT_BYTES:].view(np.int32).reshape(B, 2)
-        else:
-            self.tot = buffer[:_TOT_BYTES].view(torch.int64)
-            self.match = buffer[_TOT_BYTES:].view(torch.int32).view(B, 2)
+        self.B = B
+        super().__init__(buffer, B)
+
+    @staticmethod
+    def _fields(B):
+        return ("tot", 8, (8,)), ("match", 4, (B, 2))
 
     @staticmethod
     def empty(B, device):
-        return FormMatches(torch.empty(_TOT_BYTES + 8 * B, dtype=torch.uint8, device=device), B)
-
-    def cpu(self):
-        return self if self.is_host else FormMatches(self.buffer.cpu().numpy(), self.B)
+        return FormMatches._empty(device, B)
 
     @property
     def duplicate_of(self):
@@ -248,12 +183,6 @@ class FormMatches:
     @property
     def stock_hit(self):
         return self.match[:, 1]
-
-    def total(self, name):
-        """Entry ``name`` of ``tot`` (``TOT_FIELDS``) as a Python int; host copy only."""
-        if not self.is_host:
-            raise RuntimeError("FormMatches totals and fractions read the host copy: call .cpu() once first")
-        return int(self.tot[TOT_FIELDS.index(name)])
 
     def _over_complete(self, name):
         complete = self.B - self.total("n_truncated")
@@ -308,7 +237,6 @@ def match_forms(forms, stock=None, key_bits=64, out=None):
     elif not isinstance(out, FormMatches) or out.is_host or out.B != B or out.buffer.device != dev:
         raise ValueError("out= must be a device FormMatches of this batch's B (FormMatches.empty)")
     none = [None] * 7
-    _typed_lib()
     _lib.launch("dg_mol_canon_match", forms.buffer,
                 forms.key.data_ptr(), forms.n_atoms.data_ptr(), forms.n_bonds.data_ptr(), forms.n_splits.data_ptr(),
                 forms.canon_atoms.data_ptr(), forms.canon_bonds.data_ptr() if cap > 0 else None, B, N, cap,

@@ -16,6 +16,8 @@ namespace dg {
 char* error_buffer();
 int fail(int code, const char* fmt, ...);
 int check_launch(const char* what);
+// an entry's pointer check: `bytes` is a power of two; a null pointer is aligned
+inline bool misaligned(const void* p, uintptr_t bytes) { return reinterpret_cast<uintptr_t>(p) & (bytes - 1); }
 
 // ---- host helpers that several translation units call ----------------------------
 // out_k[c] = sum_b part[b][k][c] in a fixed order (layernorm.hip)

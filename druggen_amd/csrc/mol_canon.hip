@@ -1,4 +1,4 @@
-// Canonical forms of a decoded batch (dg_mol_canon / dg_mol_canon_match of include/druggen_hip_canon.h): an
+// Canonical forms of a decoded batch (dg_mol_canon / dg_mol_canon_match of include/druggen_hip.h): an
 // identity of a molecule that does not depend on the order of its atoms, for the reference's Uniqueness and Novelty curves
 // (src/util/utils.py:241-355) without the host.  Colour refinement with hashed neighbour sums, individualisation of the
 // smallest shared cell until the colouring is a bijection, then the graph rewritten in rank order.  Integers only; the only
@@ -9,19 +9,18 @@
 //                       bit rows (word-major: lane m reads word w of its row without bank conflicts) and the packed lower
 //                       triangle of labels.  A round is a walk over the set bits of the lane's row (mix64 per neighbour) and a
 //                       rank count: n broadcast reads of (c, sig) per lane.
-//   canon_match_rows    one workgroup per form b: the key scan of mol_stats_dups over j < b, then a binary search of the
+//   canon_match_rows    one workgroup per form b: the key scan of mol_key.h over j < b, then a binary search of the
 //                       sorted stock keys and the same scan over the run of equal keys; every key match is verified byte by byte
 //   canon_match_totals  one workgroup: tot[8]
 #include <climits>
 
 #include "common.h"
 #include "mol_key.h"
-#include "../../include/druggen_hip_canon.h"
 
 namespace dg {
 namespace {
 
-constexpr int MCN_THREADS = 256;
+constexpr int MCN_THREADS = MOL_THREADS;
 constexpr int MCN_WORDS = 8;                                 // 32-bit words of a bit row (N <= 256)
 
 __device__ __forceinline__ int tri(int i) { return (i * (i - 1)) >> 1; }      // offset of row i in the packed lower triangle
@@ -256,50 +255,6 @@ __global__ __launch_bounds__(MCN_THREADS) void mol_canon_kernel(
     }
 }
 
-// One side of a comparison: forms in their original order.
-struct Forms {
-    const int *n_atoms, *n_bonds, *n_splits;
-    const unsigned char* atoms;
-    const unsigned* bonds;
-    int cap;
-};
-
-// The scan of mol_stats_dups over the positions [p0, p1) of `o`: position p holds the key keys[p] of form index[p] (index ==
-// nullptr: form p).  A wave scans 64 keys per step, its chunks in ascending order, and verifies the key matches of a chunk one
-// after the other with all its lanes.  Returns the smallest position with a form equal to mine, p1 if there is none.  Called by
-// the whole workgroup; `first` is a shared word of its own.
-__device__ __forceinline__ int scan_equal(const Forms& o, const long long* __restrict__ keys, const int* __restrict__ index,
-                                          int p0, int p1, unsigned long long mask, unsigned long long mine, int n, int nb,
-                                          const unsigned char* my_atoms, const unsigned* my_bonds, int my_cap, int N, int* first) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid == 0) *first = p1;
-    __syncthreads();
-    const int rows = min(nb, min(my_cap, o.cap));                   // (nb itself for forms that are not truncated)
-    for (int base = p0 + 64 * wv; base < p1; base += MCN_THREADS) {
-        if (base > *static_cast<volatile int*>(first)) break;       // another wave already holds a smaller one (a hint only)
-        const int p = base + lane;
-        int idx = 0;
-        bool cand = false;
-        if (p < p1) {
-            idx = index ? index[p] : p;
-            cand = (static_cast<unsigned long long>(keys[p]) & mask) == mine && o.n_splits[idx] >= 0 && o.n_atoms[idx] == n &&
-                   o.n_bonds[idx] == nb;
-        }
-        unsigned long long matches = __ballot(cand);
-        bool found = false;
-        while (matches && !found) {
-            const int src = __ffsll(static_cast<long long>(matches)) - 1;
-            matches &= matches - 1ull;
-            const int64_t other = __shfl(idx, src, 64);
-            found = same_rows(my_atoms, o.atoms + other * N, n, my_bonds, o.bonds + other * o.cap, rows, lane);
-            if (found && lane == 0) atomicMin(first, base + src);
-        }
-        if (found) break;
-    }
-    __syncthreads();
-    return *first;
-}
-
 __global__ __launch_bounds__(MCN_THREADS) void canon_match_rows(
     const long long* __restrict__ key, Forms mine_side, int N, const long long* __restrict__ stock_keys,
     const int* __restrict__ stock_index, Forms stock, int S, unsigned long long mask, int* __restrict__ match) {
@@ -346,14 +301,8 @@ __global__ __launch_bounds__(MCN_THREADS) void canon_match_rows(
 
 __global__ __launch_bounds__(MCN_THREADS) void canon_match_totals(const int* __restrict__ match, const int* __restrict__ n_splits,
                                                                   int B, long long* __restrict__ tot) {
-    __shared__ unsigned long long acc[8];
-    const int tid = threadIdx.x, lane = tid & 63;
-    if (tid < 8) acc[tid] = 0ull;
-    __syncthreads();
-    unsigned long long part[5];                   // tot[1 .. 5]
-#pragma unroll
-    for (int k = 0; k < 5; ++k) part[k] = 0ull;
-    for (int64_t b = tid; b < B; b += MCN_THREADS) {
+    unsigned long long part[5] = {};              // tot[1 .. 5]
+    for (int64_t b = threadIdx.x; b < B; b += MCN_THREADS) {
         const int dup = match[2 * b], hit = match[2 * b + 1], split = n_splits[b];
         part[0] += dup == -1;
         part[1] += hit >= 0;
@@ -361,16 +310,8 @@ __global__ __launch_bounds__(MCN_THREADS) void canon_match_totals(const int* __r
         part[3] += split < 0;
         part[4] += split == 0;
     }
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const unsigned long long s = wave_sum(part[k]);
-        if (lane == 0) atomicAdd(&acc[k + 1], s);
-    }
-    __syncthreads();
-    if (tid < 8) tot[tid] = tid == 0 ? static_cast<long long>(B) : static_cast<long long>(acc[tid]);
+    store_totals<8>(part, B, tot);
 }
-
-inline bool misaligned(const void* p, uintptr_t bytes) { return reinterpret_cast<uintptr_t>(p) & (bytes - 1); }
 
 }  // namespace
 }  // namespace dg

@@ -6,8 +6,8 @@
 //
 // Three launches on the caller's stream:
 //   mol_stats_rows   one workgroup of 256 lanes per molecule: columns 0..6 of mol[b, :] and the molecule's 64-bit key
-//   mol_stats_dups   one workgroup per molecule b: its waves scan the keys of all j < b, 64 per step, and verify every key
-//                    match by comparing the bytes with all 64 lanes; column 7 = the smallest verified j
+//   mol_stats_dups   one workgroup per molecule b: scan_equal of mol_key.h over the keys of all j < b, every key match
+//                    verified by comparing the bytes; column 7 = the smallest verified j
 //   mol_stats_totals one workgroup: tot[16] from mol[B, 8]
 // Every element of mol and tot is stored by every call; the key workspace is rewritten before it is read.
 #include "common.h"
@@ -16,7 +16,7 @@
 namespace dg {
 namespace {
 
-constexpr int MST_THREADS = 256;
+constexpr int MST_THREADS = MOL_THREADS;
 constexpr int MST_COLS = 8;
 constexpr int MST_TOT = 16;
 
@@ -102,58 +102,28 @@ __global__ __launch_bounds__(MST_THREADS) void mol_stats_rows(
     }
 }
 
-// molecule j (n_bonds[j] == nb <= cap already known) against molecule b, byte by byte, by the 64 lanes of one wave together
-// (called in wave-uniform control flow; the answer is wave-uniform)
-__device__ __forceinline__ bool same_graph(const unsigned char* __restrict__ atoms, const unsigned* __restrict__ bonds, int N,
-                                           int cap, int nb, int64_t b, int64_t j, int lane) {
-    return same_rows(atoms + b * N, atoms + j * N, N, bonds + b * cap, bonds + j * cap, nb, lane);
-}
-
 __global__ __launch_bounds__(MST_THREADS) void mol_stats_dups(
     const unsigned char* __restrict__ atoms, const unsigned* __restrict__ bonds, const int* __restrict__ n_bonds, int N,
     int cap, const unsigned long long* __restrict__ keys, int* __restrict__ mol) {
     __shared__ int first;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int b = blockIdx.x;
     const int nb = n_bonds[b];
     if (nb > cap) {                               // truncated: its list is incomplete (uniform over the workgroup)
-        if (tid == 0) mol[static_cast<int64_t>(b) * MST_COLS + 7] = -2;
+        if (threadIdx.x == 0) mol[static_cast<int64_t>(b) * MST_COLS + 7] = -2;
         return;
     }
-    if (tid == 0) first = b;
-    __syncthreads();
-    const unsigned long long mine = keys[b];
-    const int kept = max(0, nb);
-    // a wave scans 64 keys per step, its chunks in ascending order, and verifies the key matches of a chunk one after the other
-    // with all its lanes: its first verified match is its smallest, the smallest of the four waves is the answer
-    for (int base = 64 * wv; base < b; base += MST_THREADS) {
-        if (base > *static_cast<volatile int*>(&first)) break;      // another wave already holds a smaller one (a hint only)
-        const int j = base + lane;
-        // (n_bonds[j] == nb <= cap: j is not truncated either)
-        unsigned long long matches = __ballot(j < b && keys[j] == mine && n_bonds[j] == nb);
-        bool found = false;
-        while (matches && !found) {
-            const int at = base + __ffsll(static_cast<long long>(matches)) - 1;
-            matches &= matches - 1ull;
-            found = same_graph(atoms, bonds, N, cap, kept, b, at, lane);
-            if (found && lane == 0) atomicMin(&first, at);
-        }
-        if (found) break;
-    }
-    __syncthreads();
-    if (tid == 0) mol[static_cast<int64_t>(b) * MST_COLS + 7] = first < b ? first : -1;
+    // the positional data as one side of a comparison: N atoms for everyone, nobody refused (n_bonds[j] == nb <= cap: a
+    // candidate j is not truncated either); the keys are masked already
+    const Forms all{nullptr, n_bonds, nullptr, atoms, bonds, cap};
+    const int dup = scan_equal(all, reinterpret_cast<const long long*>(keys), nullptr, 0, b, ~0ull, keys[b], N, nb,
+                               atoms + static_cast<int64_t>(b) * N, bonds + static_cast<int64_t>(b) * cap, cap, N, &first);
+    if (threadIdx.x == 0) mol[static_cast<int64_t>(b) * MST_COLS + 7] = dup < b ? dup : -1;
 }
 
 __global__ __launch_bounds__(MST_THREADS) void mol_stats_totals(const int* __restrict__ mol, const int* __restrict__ n_bonds,
                                                                 int B, int cap, long long* __restrict__ tot) {
-    __shared__ unsigned long long acc[MST_TOT];
-    const int tid = threadIdx.x, lane = tid & 63;
-    if (tid < MST_TOT) acc[tid] = 0ull;
-    __syncthreads();
-    unsigned long long part[12];                  // tot[1 .. 12]
-#pragma unroll
-    for (int c = 0; c < 12; ++c) part[c] = 0ull;
-    for (int64_t b = tid; b < B; b += MST_THREADS) {
+    unsigned long long part[12] = {};             // tot[1 .. 12]
+    for (int64_t b = threadIdx.x; b < B; b += MST_THREADS) {
         const int4 lo = *reinterpret_cast<const int4*>(mol + b * MST_COLS);
         const int4 hi = *reinterpret_cast<const int4*>(mol + b * MST_COLS + 4);
         const int col[MST_COLS] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
@@ -166,13 +136,7 @@ __global__ __launch_bounds__(MST_THREADS) void mol_stats_totals(const int* __res
         part[10] += n_bonds[b] > cap;             // truncated
         part[11] += col[2] == 1;                  // connected
     }
-#pragma unroll
-    for (int c = 0; c < 12; ++c) {
-        const unsigned long long s = wave_sum(part[c]);
-        if (lane == 0) atomicAdd(&acc[c + 1], s);
-    }
-    __syncthreads();
-    if (tid < MST_TOT) tot[tid] = tid == 0 ? static_cast<long long>(B) : static_cast<long long>(acc[tid]);
+    store_totals<MST_TOT>(part, B, tot);
 }
 
 }  // namespace
@@ -195,8 +159,7 @@ extern "C" int dg_mol_stats(const unsigned char* atoms, const unsigned char* bon
     if (!tot || (B > 0 && (!atoms || !n_bonds || !n_components || !largest_size || !mol || !workspace)))
         return fail(DG_E_ARG, "dg_mol_stats: null pointer");
     if (B > 0 && cap > 0 && !bonds) return fail(DG_E_ARG, "dg_mol_stats: null pointer (bonds with cap > 0)");
-    if ((reinterpret_cast<uintptr_t>(bonds) & 3) || (reinterpret_cast<uintptr_t>(mol) & 15) ||
-        (reinterpret_cast<uintptr_t>(tot) & 7) || (reinterpret_cast<uintptr_t>(workspace) & 7))
+    if (misaligned(bonds, 4) || misaligned(mol, 16) || misaligned(tot, 8) || misaligned(workspace, 8))
         return fail(DG_E_ARG, "dg_mol_stats: bonds must be 4-byte, mol 16-byte, tot and workspace 8-byte aligned");
     if (workspace_bytes < dg_mol_stats_workspace_bytes(B))
         return fail(DG_E_WORKSPACE, "dg_mol_stats: workspace of %zu bytes, need %zu", workspace_bytes,

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._packed import PackedRecord, uploaded
 from .functional import _c
 
 __all__ = ["argmax_labels", "decode_molecule_labels", "decode_molecule_graphs", "MoleculeBatch"]
@@ -37,27 +38,7 @@ def decode_molecule_labels(node_sample, edge_sample):
 _FIELDS = ("n_bonds", "n_components", "largest", "largest_size", "atoms", "component", "valence2", "bonds")
 
 
-def _layout(B, N, cap, with_valence):
-    """name -> (byte offset, bytes, element bytes, shape) of the packed output buffer, and its size.  Every field starts
-    on a 16-byte boundary, so each is a typed view of the ONE buffer on the device and on the host."""
-    sizes = {"n_bonds": (4, (B,)), "n_components": (4, (B,)), "largest": (4, (B,)), "largest_size": (4, (B,)),
-             "atoms": (1, (B, N)), "component": (1, (B, N)), "valence2": (2, (B, N)), "bonds": (1, (B, cap, 4))}
-    table, off = {}, 0
-    for name in _FIELDS:
-        if name == "valence2" and not with_valence:
-            continue
-        item, shape = sizes[name]
-        nbytes = item * int(np.prod(shape, dtype=np.int64))
-        table[name] = (off, nbytes, item, shape)
-        off += (nbytes + 15) & ~15
-    return table, max(off, 16)
-
-
-_TORCH_TYPES = {1: torch.uint8, 2: torch.uint16, 4: torch.int32}
-_NUMPY_TYPES = {1: np.uint8, 2: np.uint16, 4: np.int32}
-
-
-class MoleculeBatch:
+class MoleculeBatch(PackedRecord):
     """The decoded batch: typed views of one packed byte buffer.
 
     =============================================  =====================================================================
@@ -77,31 +58,19 @@ class MoleculeBatch:
     the host batch."""
 
     def __init__(self, buffer, B, N, cap, with_valence):
-        self.buffer, self.B, self.N, self.cap = buffer, B, N, cap
-        self.is_host = isinstance(buffer, np.ndarray)
-        table, total = _layout(B, N, cap, with_valence)
-        assert buffer.shape[0] == total
+        self.B, self.N, self.cap = B, N, cap
         self.valence2 = None
-        for name, (off, nbytes, item, shape) in table.items():
-            part = buffer[off:off + nbytes]
-            view = part.view(_NUMPY_TYPES[item]).reshape(shape) if self.is_host else part.view(_TORCH_TYPES[item]).view(shape)
-            setattr(self, name, view)
+        super().__init__(buffer, B, N, cap, with_valence)
+
+    @staticmethod
+    def _fields(B, N, cap, with_valence):
+        sizes = {"atoms": (1, (B, N)), "component": (1, (B, N)), "valence2": (2, (B, N)), "bonds": (1, (B, cap, 4))}
+        return [(name, *sizes.get(name, (4, (B,)))) for name in _FIELDS if name != "valence2" or with_valence]
 
     @staticmethod
     def empty(B, N, cap, with_valence, device):
         """A device batch over an uninitialised buffer (``decode_molecule_graphs(..., out=)`` fills it)."""
-        _, total = _layout(B, N, cap, with_valence)
-        return MoleculeBatch(torch.empty(total, dtype=torch.uint8, device=device), B, N, cap, with_valence)
-
-    def cpu(self):
-        """The batch on the host: one transfer of the packed buffer for all fields of all molecules."""
-        if self.is_host:
-            return self
-        return MoleculeBatch(self.buffer.cpu().numpy(), self.B, self.N, self.cap, self.valence2 is not None)
-
-    def _host(self, what):
-        if not self.is_host:
-            raise RuntimeError(f"MoleculeBatch.{what} reads the host copy: call .cpu() once for the batch first")
+        return MoleculeBatch._empty(device, B, N, cap, with_valence)
 
     @property
     def truncated(self):
@@ -123,7 +92,17 @@ class MoleculeBatch:
         return dense
 
 
-_order2_cache = {}
+_layout = MoleculeBatch.layout      # (B, N, cap, with_valence) -> (name -> (byte offset, bytes, element bytes, shape), size)
+
+
+def device_batch(batch, who, module):
+    """``who`` (a function of ``druggen_amd.<module>``) takes a device ``MoleculeBatch`` of 1 <= N <= 256."""
+    if not isinstance(batch, MoleculeBatch):
+        raise TypeError(f"{who} takes a decode.MoleculeBatch")
+    if batch.is_host or not batch.buffer.is_cuda:
+        raise RuntimeError(f"druggen_amd.{module} runs on the GPU (no CPU fallback): pass the device MoleculeBatch")
+    if not 1 <= batch.N <= 256:
+        raise ValueError(f"{who}: 1 <= N <= 256, got {batch.N}")
 
 
 def _order2_table(bond_order2, E, device):
@@ -137,11 +116,7 @@ def _order2_table(bond_order2, E, device):
         vals = tuple(int(v) for v in bond_order2)
         if any(v < 0 or v > 255 for v in vals):
             raise ValueError("bond_order2 holds twice the bond order of every bond label as a byte (0..255)")
-        t = _order2_cache.get((vals, device))      # a host sequence is uploaded once, not at every decode
-        if t is None:
-            if len(_order2_cache) > 64:
-                _order2_cache.clear()
-            t = _order2_cache[(vals, device)] = torch.tensor(vals, dtype=torch.uint8, device=device)
+        t = uploaded(vals, np.uint8, device)
     if t.dim() != 1 or t.shape[0] != E:
         raise ValueError(f"bond_order2 needs one entry per bond label ({E}), got shape {tuple(t.shape)}")
     return _c(t)

@@ -11,7 +11,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .decode import MoleculeBatch, decode_molecule_graphs
+from ._packed import PackedRecord, check_key_bits, uploaded
+from .decode import MoleculeBatch, decode_molecule_graphs, device_batch
 from .functional import _c
 
 __all__ = ["molecule_statistics", "MolStats", "StepMonitor", "fractions_of", "MOL_COLUMNS", "TOT_FIELDS"]
@@ -20,10 +21,9 @@ MOL_COLUMNS = ("atom_types", "largest_size", "n_components", "n_bonds", "over_va
                "duplicate_of")
 TOT_FIELDS = ("B", "atom_types", "largest_size", "n_components", "n_bonds", "over_valent", "changed_atoms", "changed_bonds",
               "n_over_valent", "n_copies", "n_distinct", "n_truncated", "n_connected")
-_TOT_BYTES = 16 * 8
 
 
-class MolStats:
+class MolStats(PackedRecord):
     """Statistics of one decoded batch: typed views of one packed byte buffer (``tot`` first, then ``mol``).
 
     ``mol`` [B,8] int32, one row per molecule (``MOL_COLUMNS``); a column is -1 where the input it needs was not given:
@@ -58,38 +58,32 @@ class MolStats:
 
     ``cpu()`` moves the packed buffer with ONE device->host copy; the fractions read the host copy."""
 
-    def __init__(self, buffer, B, N, workspace=None):
-        self.buffer, self.B, self.N, self._workspace = buffer, B, N, workspace
-        self.is_host = isinstance(buffer, np.ndarray)
-        assert buffer.shape[0] == _TOT_BYTES + 32 * B
-        if self.is_host:
-            self.tot = buffer[:_TOT_BYTES].view(np.int64)
-            self.mol = buffer[_TOT_BYTES:].view(np.int32).reshape(B, 8)
-        else:
-            self.tot = buffer[:_TOT_BYTES].view(torch.int64)
-            self.mol = buffer[_TOT_BYTES:].view(torch.int32).view(B, 8)
+    TOT_FIELDS = TOT_FIELDS
+
+    def __init__(self, buffer, B, N):
+        self.B, self.N, self._workspace = B, N, None
+        super().__init__(buffer, B, N)
+
+    @staticmethod
+    def _fields(B, N):
+        return ("tot", 8, (16,)), ("mol", 4, (B, 8))
 
     @staticmethod
     def empty(B, N, device):
         """Device statistics over an uninitialised buffer (``molecule_statistics(..., out=)`` fills it), with the key workspace
         of ``dg_mol_stats``."""
-        work = torch.empty(max(B, 1), dtype=torch.int64, device=device)
-        return MolStats(torch.empty(_TOT_BYTES + 32 * B, dtype=torch.uint8, device=device), B, N, work)
+        stats = MolStats._empty(device, B, N)
+        stats._workspace = torch.empty(max(B, 1), dtype=torch.int64, device=device)
+        return stats
 
     def cpu(self):
-        """The statistics on the host: one transfer for ``mol`` and ``tot``."""
-        if self.is_host:
-            return self
-        return MolStats(self.buffer.cpu().numpy(), self.B, self.N)
+        host = super().cpu()
+        if host is not self:
+            host._workspace = None      # the key workspace stays on the device
+        return host
 
     def column(self, name):
         return self.mol[:, MOL_COLUMNS.index(name)]
-
-    def total(self, name):
-        """Entry ``name`` of ``tot`` (``TOT_FIELDS``) as a Python int; host copy only."""
-        if not self.is_host:
-            raise RuntimeError("MolStats totals and fractions read the host copy: call .cpu() once first")
-        return int(self.tot[TOT_FIELDS.index(name)])
 
     def _over_b(self, name):
         return self.total(name) / self.B if self.B else float("nan")
@@ -128,9 +122,6 @@ def fractions_of(totals, N):
             "copy_fraction": t[9] / B, "over_valent_fraction": t[8] / B}
 
 
-_table_cache = {}
-
-
 def _valence_table(max_valence2, device):
     """``max_valence2`` as a contiguous uint16 device tensor (a host sequence is uploaded once)."""
     if max_valence2 is None:
@@ -145,11 +136,7 @@ def _valence_table(max_valence2, device):
         vals = tuple(int(v) for v in max_valence2)
         if any(v < 0 or v > 0xFFFF for v in vals):
             raise ValueError("max_valence2 holds twice the largest allowed valence per atom label as uint16 (0xFFFF: no limit)")
-        t = _table_cache.get((vals, device))
-        if t is None:
-            if len(_table_cache) > 64:
-                _table_cache.clear()
-            t = _table_cache[(vals, device)] = torch.from_numpy(np.asarray(vals, dtype=np.uint16)).to(device)
+        t = uploaded(vals, np.uint16, device)
     if t.dim() != 1 or not 1 <= t.shape[0] <= 256:
         raise ValueError(f"max_valence2 needs one entry per atom label (1..256), got shape {tuple(t.shape)}")
     return _c(t)
@@ -165,16 +152,10 @@ def molecule_statistics(batch, *, in_atoms=None, in_labels=None, max_valence2=No
     select candidate duplicates; every key match is verified byte by byte, so the result does not depend on it.  ``out``: a
     ``MolStats.empty(B, N, device)`` to write into.  Every element of ``mol`` and ``tot`` is written by every call; nothing is
     allocated with ``out=`` and nothing synchronises, so the call can be captured into a hipGraph."""
-    if not isinstance(batch, MoleculeBatch):
-        raise TypeError("molecule_statistics takes a decode.MoleculeBatch")
-    if batch.is_host or not batch.buffer.is_cuda:
-        raise RuntimeError("druggen_amd.monitor runs on the GPU (no CPU fallback): pass the device MoleculeBatch")
+    device_batch(batch, "molecule_statistics", "monitor")
+    check_key_bits(key_bits)
     B, N, cap = batch.B, batch.N, batch.cap
     dev = batch.buffer.device
-    if not 1 <= N <= 256:
-        raise ValueError(f"molecule_statistics: 1 <= N <= 256, got {N}")
-    if not isinstance(key_bits, int) or not 1 <= key_bits <= 64:
-        raise ValueError(f"key_bits must be an integer in 1..64, got {key_bits!r}")
     for name, t, shape, dtype in (("in_atoms", in_atoms, (B, N), torch.uint8), ("in_labels", in_labels, (B, N, N), torch.int32)):
         if t is None:
             continue

@@ -1,4 +1,4 @@
-"""Plain-Python restatement of `dg_mol_canon` and `dg_mol_canon_match` (include/druggen_hip_canon.h), written from their
+"""Plain-Python restatement of `dg_mol_canon` and `dg_mol_canon_match` (include/druggen_hip.h), written from their
 specification: loops, `sorted()` and Python integers modulo 2^64.  No keys in the matching: forms are compared as tuples in a
 double loop.  The molecules are the per-molecule dicts of tests/decode_graph_ref.py (`decode_labels`).  Also the graph families
 the host and GPU tests share."""

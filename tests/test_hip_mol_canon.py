@@ -172,6 +172,25 @@ def test_result_does_not_depend_on_the_key_width():
     assert results[0].total("n_distinct") <= 6 + 14 and results[0].total("n_in_stock") > 0 < results[0].total("n_novel")
 
 
+def test_stock_run_longer_than_one_step_of_the_scan():
+    """600 stock forms under 1 key bit: a run of equal keys is longer than the 256 positions the four waves cover per step, so
+    the scan of the stock takes a second step (within the batch only B = 257 gets that far).  One form's only copies sit at the
+    original indices 450 and 590 -- in different steps of the scan -- and the smaller one is reported; another's only copy at 530."""
+    from druggen_amd import canon
+    rng = np.random.default_rng(600)
+    N, E, S = 9, 5, 600
+    stock = [ref.molecule_like(rng, N, k % 3) for k in range(S)]
+    batch = [ref.molecule_like(rng, N, k % 3) for k in range(8)]
+    stock[450], stock[590] = ref.renumbered(rng, *batch[2]), ref.renumbered(rng, *batch[2])
+    stock[530] = ref.renumbered(rng, *batch[5])
+    stock = _stack(stock)
+    keys = canon.CanonicalSet.from_forms(canon.canonical_forms(_decode(*stock, E)), key_bits=1).keys
+    assert set(keys.tolist()) <= {0, 1} and max(int((keys == 0).sum()), int((keys == 1).sum())) > 256
+    _, matches = _check(*_stack(batch), E, stock=stock, key_bits=1)
+    assert matches.duplicate_of.tolist() == [-1] * 8
+    assert matches.stock_hit.tolist() == [-1, -1, 450, -1, -1, 530, -1, -1]
+
+
 def test_two_launches_are_bit_identical_and_no_output_is_stale():
     from druggen_amd import canon
     rng = np.random.default_rng(31)

@@ -178,7 +178,8 @@ def test_result_does_not_depend_on_the_key_width():
     assert all(np.array_equal(r.buffer, results[0].buffer) for r in results[1:])
     assert results[0].total("n_distinct") <= 6 + 13      # the pool and the near misses
     from druggen_amd import monitor
-    for bad in (0, 65, -1, 1.5, None):
+    for bad in (0, 65, -1, 1.5, None,
+                True):                         # (a bool is no width: canon's check, shared)
         with pytest.raises(ValueError, match="key_bits"):
             monitor.molecule_statistics(_decode(atoms[:2], labels[:2], 3, 3), key_bits=bad)
 
