@@ -518,7 +518,9 @@ def test_attn_core_full_size_properties():
     assert (s1 - s_def).abs().max().item() <= 1e-5 * s_def.abs().max().item()
 
 
-LN_SHAPES = [(7, 8), (33, 16), (5, 12), (1000, 128), (3, 384), (257, 32), (65, 1024), (2, 64)]
+LN_SHAPES = [(7, 8), (33, 16), (5, 12), (1000, 128), (3, 384), (257, 32), (65, 1024), (2, 64),
+             # three quads per lane (dispatched as four, the last slot masked), C = 4, a partly filled second slot, > 1024 passes
+             (5, 4), (9, 516), (3, 640), (2, 768), (6, 260), (4099, 256)]
 
 
 @pytest.mark.parametrize("R,C", LN_SHAPES)
