@@ -3,7 +3,7 @@
     python -m druggen_amd.build            # rebuild if sources are newer
     python -m druggen_amd.build --force
 The shared object has no PyTorch / pybind dependency: it is the C ABI declared
-in include/druggen_hip.h and is loaded with ctypes (druggen_amd/_lib.py).
+in include/druggen_hip.h and include/druggen_hip_text.h and is loaded with ctypes (druggen_amd/_lib.py).
 """
 from __future__ import annotations
 
@@ -17,7 +17,8 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdruggen_hip.so")
-HEADER = os.path.join(os.path.dirname(PKG), "include", "druggen_hip.h")
+INCLUDE = os.path.join(os.path.dirname(PKG), "include")
+HEADERS = [os.path.join(INCLUDE, "druggen_hip.h"), os.path.join(INCLUDE, "druggen_hip_text.h")]
 ARCH = "gfx950"
 
 
@@ -29,7 +30,7 @@ def _stale() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + [HEADER]
+    deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + HEADERS
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -41,7 +42,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         raise RuntimeError("hipcc not found: cannot build libdruggen_hip.so")
     os.makedirs(LIB_DIR, exist_ok=True)
     objs, jobs = [], []
-    headers = glob.glob(os.path.join(CSRC, "*.h")) + [HEADER]
+    headers = glob.glob(os.path.join(CSRC, "*.h")) + HEADERS
     for src in sources():
         obj = os.path.join(LIB_DIR, os.path.basename(src) + ".o")
         objs.append(obj)

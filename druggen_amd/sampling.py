@@ -12,6 +12,7 @@ import torch
 
 from .decode import _order2_table, decode_molecule_graphs
 from .functional import (activation_dtype, as_one_hot, attach_one_hot_labels, bump_weights_epoch, one_hot_labels)
+from .smiles_out import SmilesTables, write_smiles
 
 __all__ = ["MoleculeSampler"]
 
@@ -29,12 +30,20 @@ class MoleculeSampler:
     ``G`` runs in ``eval()`` under ``torch.inference_mode()``; its training flags are restored.  In-place weight updates
     (``load_state_dict``, an optimizer step) are seen by the next ``sample`` in both modes; parameters that were MOVED
     since the capture (``optim.FlatAdamW`` re-points them into its flat buffer at its first step) make ``sample`` capture
-    again."""
+    again.
 
-    def __init__(self, G, edge, node, *, graph: bool = True, bond_order2=None, bond_cap=None, warmup: int = 3):
+    ``smiles``: ``smiles_out.SmilesTables`` on the batch's device -- every sample then also writes the SMILES string of each
+    molecule's largest fragment (``smiles_out.write_smiles``: one more launch behind the decode, inside the captured graph when
+    there is one), and ``sampler.smiles`` is the ``SmilesBatch`` of the last sample (graphed: a static buffer like the
+    ``MoleculeBatch``).  None: nothing is written and ``sampler.smiles`` stays None."""
+
+    def __init__(self, G, edge, node, *, graph: bool = True, bond_order2=None, bond_cap=None, warmup: int = 3, smiles=None):
         if not (edge.is_cuda and node.is_cuda):
             raise RuntimeError("druggen_amd.sampling runs on the GPU (no CPU fallback)")
+        if smiles is not None and not isinstance(smiles, SmilesTables):
+            raise TypeError("smiles= takes smiles_out.SmilesTables (SmilesTables.from_decoders)")
         self.G = G
+        self.smiles_tables, self.smiles = smiles, None
         self.bond_cap = bond_cap
         self._order2 = _order2_table(bond_order2, edge.shape[-1], node.device)      # on the device before any capture
         self.graph = None
@@ -77,6 +86,8 @@ class MoleculeSampler:
             with torch.inference_mode():
                 _, _, node_sample, edge_sample = self.G(edge, node)
                 batch = decode_molecule_graphs(node_sample, edge_sample, bond_order2=self._order2, bond_cap=self.bond_cap)
+                if self.smiles_tables is not None:
+                    self.smiles = write_smiles(batch, self.smiles_tables)
         finally:
             for m, was in modes:
                 m.training = was
