@@ -8,8 +8,9 @@ A ChEMBL-sized stock of 1.6 M 1024-bit fingerprints is 200 MB this way instead o
 (csrc/fp_tanimoto.hip) computes for every generated row the maximum (and where it is attained) or the mean
 of ``float32(c) / float32(a + b - c)`` over the stock -- the reference's float32 quotient, 0 / 0 taken as 1.
 
-GPU only, no CPU fallback.  The Morgan fingerprints themselves still come from RDKit on the host; this module starts
-from their bits."""
+GPU only, no CPU fallback.  This module starts from bits: RDKit's Morgan fingerprints come from the host as dense rows
+(``pack_fingerprints``); ``druggen_amd.fingerprint`` makes the project's own circular fingerprints of decoded molecules on the
+device and hands them over as ``PackedFingerprints``."""
 from __future__ import annotations
 
 from dataclasses import dataclass
