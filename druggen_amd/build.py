@@ -3,7 +3,8 @@
     python -m druggen_amd.build            # rebuild if sources are newer
     python -m druggen_amd.build --force
 The shared object has no PyTorch / pybind dependency: it is the C ABI declared
-in include/druggen_hip.h, include/druggen_hip_text.h and include/druggen_hip_fp.h and is loaded with ctypes (druggen_amd/_lib.py).
+in include/druggen_hip.h, include/druggen_hip_text.h, include/druggen_hip_fp.h and include/druggen_hip_valid.h and is loaded
+with ctypes (druggen_amd/_lib.py).
 """
 from __future__ import annotations
 
@@ -19,7 +20,7 @@ LIB_DIR = os.path.join(PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdruggen_hip.so")
 INCLUDE = os.path.join(os.path.dirname(PKG), "include")
 HEADERS = [os.path.join(INCLUDE, "druggen_hip.h"), os.path.join(INCLUDE, "druggen_hip_text.h"),
-           os.path.join(INCLUDE, "druggen_hip_fp.h")]
+           os.path.join(INCLUDE, "druggen_hip_fp.h"), os.path.join(INCLUDE, "druggen_hip_valid.h")]
 ARCH = "gfx950"
 
 

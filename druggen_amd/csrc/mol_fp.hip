@@ -8,17 +8,15 @@
 //                   global memory and is walked once per phase -- scope, degrees, ring flags, every layer's neighbour sums --
 //                   so no bond count is refused.  A hash of K selects candidates, the words of K decide.
 #include "mol_key.h"
+#include "mol_ring.h"
 #include "../../include/druggen_hip_fp.h"
 
 namespace dg {
 namespace {
 
 constexpr int MFP_MAX = 256;                                     // atoms, labels, threads
-constexpr int MFP_NONE = 0xFFFF;                                 // no parent
 typedef unsigned long long u64;
 
-// words of a bit row in LDS: odd, so that the rows of neighbouring atoms start on different banks
-__host__ __device__ constexpr int row_stride(int N) { return ((N + 31) >> 5) | 1; }
 // ids of R + 1 layers, the neighbour sums, adjacency + two balls + R layers of K, R layers of hashes
 __host__ __device__ constexpr int lds_bytes(int N, int R) {
     return (R + 2) * N * 8 + (3 + R) * N * row_stride(N) * 4 + R * N * 4;
@@ -65,7 +63,7 @@ __global__ __launch_bounds__(MFP_MAX) void mol_fp_kernel(
     for (int w = tid; w < N * S; w += nt) adj[w] = 0u;
     for (int i = tid; i < MFP_MAX; i += nt) {
         deg[i] = val2[i] = 0u;
-        parent[i] = MFP_NONE;
+        parent[i] = RING_NONE;
         depth[i] = 0;
         member[i] = ring[i] = cov[i] = 0;
         lab_a[i] = i < N ? atoms[b * N + i] : 0;
@@ -110,62 +108,9 @@ __global__ __launch_bounds__(MFP_MAX) void mol_fp_kernel(
     __syncthreads();
     if (tid < N && deg[tid]) atomicOr(&bonded[tid >> 5], 1u << (tid & 31));
 
-    // ---- a breadth-first forest over the bonded atoms: one level, or one new root, per turn (at most 2 N turns) ----
-    for (int turn = 0; turn < 2 * N + 2; ++turn) {
-        __syncthreads();                                            // front and vis are final
-        bool any_front = false;
-        int first = -1;                                             // the smallest bonded atom not reached yet
-        for (int w = W - 1; w >= 0; --w) {
-            any_front |= front[w] != 0u;
-            const unsigned open = bonded[w] & ~vis[w];
-            if (open) first = 32 * w + __ffs(open) - 1;
-        }
-        if (first < 0) break;                                       // (every thread read the same words)
-        bool take = false;
-        int par = MFP_NONE, dep = 0;
-        if (tid < N && deg[tid] && !((vis[tid >> 5] >> (tid & 31)) & 1u)) {
-            if (!any_front) {
-                take = tid == first;
-            } else {
-                for (int w = 0; w < W; ++w) {
-                    const unsigned hit = adj[tid * S + w] & front[w];
-                    if (hit) {
-                        par = 32 * w + __ffs(hit) - 1;
-                        dep = depth[par] + 1;
-                        take = true;
-                        break;
-                    }
-                }
-            }
-        }
-        __syncthreads();                                            // everyone has read front and vis
-        if (tid < 8) front[tid] = 0u;
-        __syncthreads();
-        if (take) {
-            parent[tid] = static_cast<unsigned short>(par);
-            depth[tid] = static_cast<unsigned short>(dep);
-            atomicOr(&front[tid >> 5], 1u << (tid & 31));
-            atomicOr(&vis[tid >> 5], 1u << (tid & 31));
-        }
-    }
-    __syncthreads();
-
-    // ---- ring flags: a bond outside the forest closes a cycle with the two tree paths to the ends' common ancestor ----
-    for (int k = tid; k < kept; k += nt) {
-        const unsigned row = list[k];
-        const int i = row & 255u, j = (row >> 8) & 255u;
-        if (i >= N || j >= N || i == j || !member[i] || !member[j]) continue;
-        if (parent[i] == j || parent[j] == i) continue;             // a tree bond
-        ring[i] = ring[j] = 1;
-        int u = i, v = j;
-        for (int step = 0; step < 2 * N && u != v; ++step) {        // the deeper end climbs
-            int& up = depth[u] >= depth[v] ? u : v;
-            const int p = parent[up];
-            if (p == MFP_NONE) break;                               // (the ends of a bond share a tree)
-            cov[up] = 1;
-            up = p;
-        }
-    }
+    // ---- ring flags (mol_ring.h): a breadth-first forest, then the tree paths that the bonds outside it close ----
+    ring_forest(N, adj, deg, bonded, front, vis, parent, depth);
+    ring_cover(N, list, kept, member, parent, depth, cov, ring);
     __syncthreads();
     if (tid < N && cov[tid]) {
         ring[tid] = 1;

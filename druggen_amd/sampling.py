@@ -13,6 +13,7 @@ import torch
 from .decode import _order2_table, decode_molecule_graphs
 from .functional import (activation_dtype, as_one_hot, attach_one_hot_labels, bump_weights_epoch, one_hot_labels)
 from .smiles_out import SmilesTables, write_smiles
+from .validity import ValenceTables, check_molecules
 
 __all__ = ["MoleculeSampler"]
 
@@ -35,15 +36,24 @@ class MoleculeSampler:
     ``smiles``: ``smiles_out.SmilesTables`` on the batch's device -- every sample then also writes the SMILES string of each
     molecule's largest fragment (``smiles_out.write_smiles``: one more launch behind the decode, inside the captured graph when
     there is one), and ``sampler.smiles`` is the ``SmilesBatch`` of the last sample (graphed: a static buffer like the
-    ``MoleculeBatch``).  None: nothing is written and ``sampler.smiles`` stays None."""
+    ``MoleculeBatch``).  None: nothing is written and ``sampler.smiles`` stays None.
 
-    def __init__(self, G, edge, node, *, graph: bool = True, bond_order2=None, bond_cap=None, warmup: int = 3, smiles=None):
+    ``validity``: ``validity.ValenceTables`` on the batch's device -- every sample then also checks each molecule's largest
+    fragment (``validity.check_molecules``: one more launch behind the decode, inside the captured graph when there is one); the
+    ``MoleculeValidity`` is ``batch.validity`` of the returned batch and ``sampler.validity`` (graphed: a static buffer like the
+    ``MoleculeBatch``).  None: nothing is checked and both stay None."""
+
+    def __init__(self, G, edge, node, *, graph: bool = True, bond_order2=None, bond_cap=None, warmup: int = 3, smiles=None,
+                 validity=None):
         if not (edge.is_cuda and node.is_cuda):
             raise RuntimeError("druggen_amd.sampling runs on the GPU (no CPU fallback)")
         if smiles is not None and not isinstance(smiles, SmilesTables):
             raise TypeError("smiles= takes smiles_out.SmilesTables (SmilesTables.from_decoders)")
+        if validity is not None and not isinstance(validity, ValenceTables):
+            raise TypeError("validity= takes validity.ValenceTables (ValenceTables.from_decoders)")
         self.G = G
         self.smiles_tables, self.smiles = smiles, None
+        self.validity_tables, self.validity = validity, None
         self.bond_cap = bond_cap
         self._order2 = _order2_table(bond_order2, edge.shape[-1], node.device)      # on the device before any capture
         self.graph = None
@@ -88,6 +98,8 @@ class MoleculeSampler:
                 batch = decode_molecule_graphs(node_sample, edge_sample, bond_order2=self._order2, bond_cap=self.bond_cap)
                 if self.smiles_tables is not None:
                     self.smiles = write_smiles(batch, self.smiles_tables)
+                if self.validity_tables is not None:
+                    self.validity = batch.validity = check_molecules(batch, self.validity_tables)
         finally:
             for m, was in modes:
                 m.training = was
