@@ -41,59 +41,76 @@ __global__ void onehot_kernel(const int* __restrict__ labels, int64_t rows, int 
 // ---- AdamW over a flat buffer ---------------------------------------------------------------
 // torch.optim.AdamW single-tensor formulas: p *= 1 - lr*wd;  m = b1 m + (1-b1) g;
 // v = b2 v + (1-b2) g^2;  p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
+// One element, the same arithmetic on every path (float4 body, scalar tail, scalar kernel, device-step kernel), so that
+// they agree bit for bit.  Under -ffp-contract=fast the compiler decides per kernel which product it contracts into the
+// sum that follows (packed in one kernel, separate in the next), so the roundings are spelled out: the one multiply-add
+// is an fmaf, and a product that is rounded before its sum goes through `rounded`.  decay = fmaf(-lr, wd, 1), step = lr / bc1.
+__device__ __forceinline__ float rounded(float x) {
+    asm("" : "+v"(x));      // no instruction: the value only becomes opaque, so it cannot be fused into what consumes it
+    return x;
+}
+
+__device__ __forceinline__ void adamw_update(float& p, float g, float& m, float& v, float decay, float step, float beta1,
+                                             float beta2, float eps, float bc2_sqrt) {
+    m = fmaf(1.0f - beta1, g, beta1 * m);
+    v = rounded((1.0f - beta2) * g * g) + rounded(beta2 * v);
+    p = rounded(p * decay) - step * m / (sqrtf(v) / bc2_sqrt + eps);
+}
+
+// VEC: every pointer is 16-byte aligned -- four elements per thread through float4, a scalar tail of n % 4 elements;
+// otherwise one element per thread (no access wider than a float).
+template <bool VEC>
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                             float* __restrict__ v, int64_t n, float lr, float beta1, float beta2, float eps,
-                             float weight_decay, float bc1, float bc2_sqrt) {
-    const int64_t i4 = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) * 4;
+                             float* __restrict__ v, int64_t n, float decay, float step, float beta1, float beta2,
+                             float eps, float bc2_sqrt) {
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (!VEC) {
+        if (t < n) adamw_update(p[t], g[t], m[t], v[t], decay, step, beta1, beta2, eps, bc2_sqrt);
+        return;
+    }
+    const int64_t i4 = t * 4;
     if (i4 >= n) return;
-    const float step = lr / bc1;
     if (i4 + 3 < n) {
         float4 pp = ld4(p + i4), gg = ld4(g + i4), mm = ld4(m + i4), vv = ld4(v + i4);
         float* pe = &pp.x; float* ge = &gg.x; float* me = &mm.x; float* ve = &vv.x;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            pe[k] *= 1.0f - lr * weight_decay;
-            me[k] = beta1 * me[k] + (1.0f - beta1) * ge[k];
-            ve[k] = beta2 * ve[k] + (1.0f - beta2) * ge[k] * ge[k];
-            pe[k] -= step * me[k] / (sqrtf(ve[k]) / bc2_sqrt + eps);
-        }
+        for (int k = 0; k < 4; ++k) adamw_update(pe[k], ge[k], me[k], ve[k], decay, step, beta1, beta2, eps, bc2_sqrt);
         st4(p + i4, pp);
         st4(m + i4, mm);
         st4(v + i4, vv);
     } else {
-        for (int64_t i = i4; i < n; ++i) {
-            float pp = p[i] * (1.0f - lr * weight_decay);
-            const float gg = g[i];
-            const float mm = beta1 * m[i] + (1.0f - beta1) * gg;
-            const float vv = beta2 * v[i] + (1.0f - beta2) * gg * gg;
-            pp -= step * mm / (sqrtf(vv) / bc2_sqrt + eps);
-            p[i] = pp;
-            m[i] = mm;
-            v[i] = vv;
-        }
+        for (int64_t i = i4; i < n; ++i) adamw_update(p[i], g[i], m[i], v[i], decay, step, beta1, beta2, eps, bc2_sqrt);
     }
 }
 
 // Graph-replay-safe variant: the step count lives in device memory, so a captured launch computes
-// fresh bias corrections on every replay (host-side scalars would be frozen into the graph).
+// fresh bias corrections on every replay (host-side scalars would be frozen into the graph).  The counter is incremented
+// first (adamw_bump_kernel), then read.  The corrections are dg_adamw_flat's: 1 - beta^t in double from the float betas,
+// the square root in double, each rounded to float once -- by one thread per block of ADAMW_DEV_ELEMS elements (in float,
+// beta2^t is rounded next to 1 before the subtraction: a relative error of 2^-24 / (t (1 - beta2)) in bc2 from step 2 on).
 __global__ void adamw_bump_kernel(int* step) { *step += 1; }
 
-__global__ void adamw_devstep_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                     float* __restrict__ v, int64_t n, float lr, float beta1, float beta2, float eps,
-                                     float weight_decay, const int* __restrict__ step) {
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float t = static_cast<float>(*step);
-    const float bc1 = 1.0f - powf(beta1, t);
-    const float bc2_sqrt = sqrtf(1.0f - powf(beta2, t));
-    float pp = p[i] * (1.0f - lr * weight_decay);
-    const float gg = g[i];
-    const float mm = beta1 * m[i] + (1.0f - beta1) * gg;
-    const float vv = beta2 * v[i] + (1.0f - beta2) * gg * gg;
-    pp -= (lr / bc1) * mm / (sqrtf(vv) / bc2_sqrt + eps);
-    p[i] = pp;
-    m[i] = mm;
-    v[i] = vv;
+constexpr int ADAMW_DEV_PER_THREAD = 4;
+constexpr int ADAMW_DEV_ELEMS = 256 * ADAMW_DEV_PER_THREAD;
+
+__global__ __launch_bounds__(256) void adamw_devstep_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                            float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                            float lr, float decay, float beta1, float beta2, float eps,
+                                                            const int* __restrict__ step) {
+    __shared__ float bc[2];
+    if (threadIdx.x == 0) {
+        const double t = static_cast<double>(*step);
+        bc[0] = static_cast<float>(1.0 - pow(static_cast<double>(beta1), t));
+        bc[1] = static_cast<float>(sqrt(1.0 - pow(static_cast<double>(beta2), t)));
+    }
+    __syncthreads();
+    const float stp = lr / bc[0], bc2_sqrt = bc[1];
+    const int64_t base = static_cast<int64_t>(blockIdx.x) * ADAMW_DEV_ELEMS + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < ADAMW_DEV_PER_THREAD; ++k) {
+        const int64_t i = base + k * 256;
+        if (i < n) adamw_update(p[i], g[i], m[i], v[i], decay, stp, beta1, beta2, eps, bc2_sqrt);
+    }
 }
 
 // ---- argmax decode --------------------------------------------------------------------------
@@ -224,6 +241,9 @@ extern "C" int dg_densify(const int64_t* edge_src, const int64_t* edge_dst, cons
     return check_launch("dg_densify");
 }
 
+// 1 - lr*wd with one rounding, on the host, for both entries
+static float adamw_decay(float lr, float weight_decay) { return fmaf(-lr, weight_decay, 1.0f); }
+
 extern "C" int dg_adamw_flat(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                              float beta1, float beta2, float eps, float weight_decay, int64_t step,
                              dg_stream_t stream_) {
@@ -232,10 +252,19 @@ extern "C" int dg_adamw_flat(float* param, const float* grad, float* exp_avg, fl
     if (n == 0) return 0;
     const double bc1 = 1.0 - pow(static_cast<double>(beta1), static_cast<double>(step));
     const double bc2 = 1.0 - pow(static_cast<double>(beta2), static_cast<double>(step));
-    const int64_t threads = (n + 3) / 4;
-    hipLaunchKernelGGL(adamw_kernel, dim3(static_cast<unsigned>((threads + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream_), param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
-                       weight_decay, static_cast<float>(bc1), static_cast<float>(sqrt(bc2)));
+    const float stp = lr / static_cast<float>(bc1), bc2_sqrt = static_cast<float>(sqrt(bc2));
+    const float decay = adamw_decay(lr, weight_decay);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const bool vec = ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) |
+                       reinterpret_cast<uintptr_t>(exp_avg) | reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) == 0;
+    const int64_t threads = vec ? (n + 3) / 4 : n;
+    const dim3 grid(static_cast<unsigned>((threads + 255) / 256));
+    if (vec)
+        hipLaunchKernelGGL(adamw_kernel<true>, grid, dim3(256), 0, stream, param, grad, exp_avg, exp_avg_sq, n, decay, stp,
+                           beta1, beta2, eps, bc2_sqrt);
+    else
+        hipLaunchKernelGGL(adamw_kernel<false>, grid, dim3(256), 0, stream, param, grad, exp_avg, exp_avg_sq, n, decay, stp,
+                           beta1, beta2, eps, bc2_sqrt);
     return check_launch("dg_adamw_flat");
 }
 
@@ -248,8 +277,9 @@ extern "C" int dg_adamw_flat_devstep(float* param, const float* grad, float* exp
     if (n == 0) return 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     hipLaunchKernelGGL(adamw_bump_kernel, dim3(1), dim3(1), 0, stream, step_counter);
-    hipLaunchKernelGGL(adamw_devstep_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, stream, param,
-                       grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step_counter);
+    hipLaunchKernelGGL(adamw_devstep_kernel, dim3(static_cast<unsigned>((n + ADAMW_DEV_ELEMS - 1) / ADAMW_DEV_ELEMS)),
+                       dim3(256), 0, stream, param, grad, exp_avg, exp_avg_sq, n, lr, adamw_decay(lr, weight_decay), beta1,
+                       beta2, eps, step_counter);
     return check_launch("dg_adamw_flat_devstep");
 }
 

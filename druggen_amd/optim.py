@@ -6,7 +6,8 @@ The live parameters (those that received a gradient at the first step -- the
 Discriminator's dead last-block edge branch never does, and torch skips
 ``grad is None`` parameters entirely) are re-pointed to views of one flat fp32
 buffer; gradients are packed into a matching flat buffer, which is also the
-bucket the data-parallel all-reduce runs on (``trainer.GANStep``).
+bucket the data-parallel all-reduce runs on (``trainer.GANStep``).  The set is
+fixed by the first step: a later step with another set raises.
 """
 from __future__ import annotations
 
@@ -43,13 +44,6 @@ class FlatAdamW:
         ps = [self.params[i] for i in live]
         dev = ps[0].device
         n = sum(p.numel() for p in ps)
-        old_m, old_v = {}, {}
-        if self._live is not None:      # liveness changed: carry the moments over
-            off = 0
-            for i in self._live:
-                k = self.params[i].numel()
-                old_m[i], old_v[i] = self.exp_avg[off:off + k].clone(), self.exp_avg_sq[off:off + k].clone()
-                off += k
         self.flat_param = torch.empty(n, dtype=torch.float32, device=dev)
         self.flat_grad = torch.empty(n, dtype=torch.float32, device=dev)
         self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -62,9 +56,6 @@ class FlatAdamW:
                 self.flat_param[off:off + k].copy_(p.data.reshape(-1))
                 p.data = self.flat_param[off:off + k].view_as(p)
                 self._grad_views.append(self.flat_grad[off:off + k].view_as(p))
-                if i in old_m:
-                    self.exp_avg[off:off + k].copy_(old_m[i])
-                    self.exp_avg_sq[off:off + k].copy_(old_v[i])
                 off += k
         self._live = list(live)
 
@@ -75,8 +66,17 @@ class FlatAdamW:
             return None
         if not self.params[live[0]].is_cuda:
             raise RuntimeError("FlatAdamW runs on the GPU (no CPU fallback)")
-        if live != self._live:
+        if self._live is None:
             self._build(live)
+        elif live != self._live:
+            # one step count serves the whole flat buffer (torch.optim.AdamW keeps one per parameter): a parameter that
+            # joined now would be bias-corrected as if it had been stepped from the start
+            was, what = set(self._live), lambda i: f"#{i} {tuple(self.params[i].shape)}"
+            joined = ", ".join(what(i) for i in live if i not in was) or "none"
+            left = ", ".join(what(i) for i in self._live if i not in set(live)) or "none"
+            raise RuntimeError("FlatAdamW: the set of parameters that receive a gradient changed after the first step "
+                               f"(joined: {joined}; left: {left}); give every live parameter a gradient at every step "
+                               "or build a new optimizer")
         torch._foreach_copy_(self._grad_views, [self.params[i].grad for i in live])
         return self.flat_grad
 

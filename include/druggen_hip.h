@@ -619,13 +619,21 @@ int dg_mol_gather_features(const uint8_t* atoms, const int64_t* ptr, const uint3
                            float* x, int* bad_index, dg_stream_t stream);
 
 /* dg_adamw_flat: one torch.optim.AdamW update (reference train.py:213-214,368,384;
- * decoupled weight decay, no amsgrad) over flat float32 buffers; `step` >= 1.       */
+ * decoupled weight decay, no amsgrad) over flat float32 buffers of n elements; `step` >= 1 is the count of THIS update.
+ * The bias corrections 1 - beta^step are evaluated in double from the float betas and rounded to float once; the decay
+ * factor is 1 - lr*weight_decay rounded to float once.  `grad` is only read, nothing past element n - 1 is
+ * touched.  Pointers need no more than float alignment: when all four are 16-byte aligned the body moves float4s,
+ * otherwise every access is a single float -- the results are the same bit for bit.  A null pointer, n < 0 or step < 1:
+ * DG_E_ARG.  n == 0 returns 0 without a launch.                                                                      */
 int dg_adamw_flat(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                   float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
                   dg_stream_t stream);
 
-/* Same update with the step count in device memory (`step_counter`, int32, incremented by the
- * call): safe to capture into a hipGraph and replay.                                */
+/* Same update with the step count in device memory (`step_counter`, one int32): safe to capture into a hipGraph and
+ * replay.  The call FIRST increments the counter, THEN uses the new value as dg_adamw_flat's `step` (a counter of 0 before
+ * the first call; it reads t after the t-th), with the same bias corrections -- double, rounded once -- and the same
+ * arithmetic per element.  Float alignment suffices.  A null pointer (the counter included) or n < 0: DG_E_ARG.  n == 0
+ * returns 0 without a launch: nothing is touched and the counter is NOT incremented.                                   */
 int dg_adamw_flat_devstep(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                           float lr, float beta1, float beta2, float eps, float weight_decay,
                           int* step_counter, dg_stream_t stream);
