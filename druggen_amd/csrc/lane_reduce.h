@@ -53,4 +53,22 @@ __device__ __forceinline__ float half_wave_total_swap(float x) {
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
+// Integer sum over the 64 lanes of a wave, result in every lane (mol_desc.hip): the four row steps above, then the rows meet
+// through v_permlane16_swap / v_permlane32_swap of the value with itself, as in common.h's xor_step.  Every lane of the wave
+// must be active.
+template <int CTRL>
+__device__ __forceinline__ unsigned usum_dpp(unsigned x) {
+    return x + static_cast<unsigned>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), CTRL, 0xF, 0xF, true));
+}
+__device__ __forceinline__ unsigned wave_usum(unsigned x) {
+    x = usum_dpp<0xB1>(x);
+    x = usum_dpp<0x4E>(x);
+    x = usum_dpp<0x141>(x);
+    x = usum_dpp<0x140>(x);
+    auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+    x = r[0] + r[1];
+    r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
+    return r[0] + r[1];
+}
+
 }  // namespace dg

@@ -14,6 +14,7 @@ from .decode import _order2_table, decode_molecule_graphs
 from .functional import (activation_dtype, as_one_hot, attach_one_hot_labels, bump_weights_epoch, one_hot_labels)
 from .smiles_out import SmilesTables, write_smiles
 from .validity import ValenceTables, check_molecules
+from .descriptors import DescriptorTables, describe_molecules
 
 __all__ = ["MoleculeSampler"]
 
@@ -41,19 +42,29 @@ class MoleculeSampler:
     ``validity``: ``validity.ValenceTables`` on the batch's device -- every sample then also checks each molecule's largest
     fragment (``validity.check_molecules``: one more launch behind the decode, inside the captured graph when there is one); the
     ``MoleculeValidity`` is ``batch.validity`` of the returned batch and ``sampler.validity`` (graphed: a static buffer like the
-    ``MoleculeBatch``).  None: nothing is checked and both stay None."""
+    ``MoleculeBatch``).  None: nothing is checked and both stay None.
+
+    ``descriptors``: ``descriptors.DescriptorTables`` on the batch's device, together with ``validity=`` (``ValueError``
+    without it: the descriptors are made of the verdicts) -- every sample then also describes each molecule's largest fragment
+    (``descriptors.describe_molecules``: one more launch behind the check, inside the captured graph when there is one); the
+    ``MoleculeDescriptors`` is ``batch.descriptors`` and ``sampler.descriptors``.  None: both stay None."""
 
     def __init__(self, G, edge, node, *, graph: bool = True, bond_order2=None, bond_cap=None, warmup: int = 3, smiles=None,
-                 validity=None):
+                 validity=None, descriptors=None):
         if not (edge.is_cuda and node.is_cuda):
             raise RuntimeError("druggen_amd.sampling runs on the GPU (no CPU fallback)")
         if smiles is not None and not isinstance(smiles, SmilesTables):
             raise TypeError("smiles= takes smiles_out.SmilesTables (SmilesTables.from_decoders)")
         if validity is not None and not isinstance(validity, ValenceTables):
             raise TypeError("validity= takes validity.ValenceTables (ValenceTables.from_decoders)")
+        if descriptors is not None and not isinstance(descriptors, DescriptorTables):
+            raise TypeError("descriptors= takes descriptors.DescriptorTables (DescriptorTables.from_decoders)")
+        if descriptors is not None and validity is None:
+            raise ValueError("descriptors= needs validity= as well: the descriptors are made of the validity check's verdicts")
         self.G = G
         self.smiles_tables, self.smiles = smiles, None
         self.validity_tables, self.validity = validity, None
+        self.descriptor_tables, self.descriptors = descriptors, None
         self.bond_cap = bond_cap
         self._order2 = _order2_table(bond_order2, edge.shape[-1], node.device)      # on the device before any capture
         self.graph = None
@@ -100,6 +111,8 @@ class MoleculeSampler:
                     self.smiles = write_smiles(batch, self.smiles_tables)
                 if self.validity_tables is not None:
                     self.validity = batch.validity = check_molecules(batch, self.validity_tables)
+                if self.descriptor_tables is not None:
+                    self.descriptors = batch.descriptors = describe_molecules(batch, batch.validity, self.descriptor_tables)
         finally:
             for m, was in modes:
                 m.training = was
