@@ -45,6 +45,9 @@ __device__ __forceinline__ u32x2_t tr_read(unsigned addr) {
     return __builtin_bit_cast(u32x2_t, v);
 }
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+// d * act'(x) for x <= 0.  relu (slope 0) gives exactly zero, as autograd's threshold_backward does: 0 * d would turn a
+// non-finite upstream gradient into NaN at a masked element
+__device__ __forceinline__ float act_bwd_neg(float d, float slope) { return slope != 0.f ? slope * d : 0.f; }
 __device__ __forceinline__ f32x2 up2(unsigned w) { return f32x2{lo_bf16(w), hi_bf16(w)}; }
 
 struct EmbBwdArgs {
@@ -237,10 +240,10 @@ __global__ __launch_bounds__(512, 2) void embed_bwd_bf16_kernel(const EmbBwdArgs
             for (int mb = 0; mb < MB; ++mb) {
                 const u32x2_t x1 = tr_read(ga + mb * 4096), x2 = tr_read(ga + GB + mb * 4096);
                 f32x2 d0 = (up2(x1[0]) + up2(x2[0])) * f32x2{0.5f, 0.5f}, d1 = (up2(x1[1]) + up2(x2[1])) * f32x2{0.5f, 0.5f};
-                d0[0] = pre[mb][0] > 0.f ? d0[0] : p.slope * d0[0];
-                d0[1] = pre[mb][1] > 0.f ? d0[1] : p.slope * d0[1];
-                d1[0] = pre[mb][2] > 0.f ? d1[0] : p.slope * d1[0];
-                d1[1] = pre[mb][3] > 0.f ? d1[1] : p.slope * d1[1];
+                d0[0] = pre[mb][0] > 0.f ? d0[0] : act_bwd_neg(d0[0], p.slope);
+                d0[1] = pre[mb][1] > 0.f ? d0[1] : act_bwd_neg(d0[1], p.slope);
+                d1[0] = pre[mb][2] > 0.f ? d1[0] : act_bwd_neg(d1[0], p.slope);
+                d1[1] = pre[mb][3] > 0.f ? d1[1] : act_bwd_neg(d1[1], p.slope);
                 dA[mb][0] = pack_bf16(d0[0], d0[1]);
                 dA[mb][1] = pack_bf16(d1[0], d1[1]);
                 const f32x2 q0 = up2(dA[mb][0]), q1 = up2(dA[mb][1]);      // db2 of the values the GEMMs see
@@ -281,10 +284,10 @@ __global__ __launch_bounds__(512, 2) void embed_bwd_bf16_kernel(const EmbBwdArgs
                 const u32x2_t hv = tr_read(ha + mb * 2048);        // h of (rows, this unit): act'(pre1) from its sign
                 const f32x2 h0 = up2(hv[0]), h1 = up2(hv[1]);
                 float d[4];
-                d[0] = h0[0] > 0.f ? dh[0] : p.slope * dh[0];
-                d[1] = h0[1] > 0.f ? dh[1] : p.slope * dh[1];
-                d[2] = h1[0] > 0.f ? dh[2] : p.slope * dh[2];
-                d[3] = h1[1] > 0.f ? dh[3] : p.slope * dh[3];
+                d[0] = h0[0] > 0.f ? dh[0] : act_bwd_neg(dh[0], p.slope);
+                d[1] = h0[1] > 0.f ? dh[1] : act_bwd_neg(dh[1], p.slope);
+                d[2] = h1[0] > 0.f ? dh[2] : act_bwd_neg(dh[2], p.slope);
+                d[3] = h1[1] > 0.f ? dh[3] : act_bwd_neg(dh[3], p.slope);
                 const unsigned k0 = pack_bf16(d[0], d[1]), k1 = pack_bf16(d[2], d[3]);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -409,6 +412,11 @@ extern "C" int dg_embed_sym_bwd_bf16(const float* a, const float* w1, const floa
                                      dg_stream_t stream_) {
     if (!a || !w1 || !b1 || !w2 || !b2 || !g || !dw1 || !db1 || !dw2 || !db2 || !workspace)
         return fail(DG_E_ARG, "dg_embed_sym_bwd_bf16: null pointer");
+    // 16-byte LDS-DMA of the gradient rows, float4 partial sums in the workspace
+    if (misaligned(g, 16) || misaligned(workspace, 16) || misaligned(a, 4) || misaligned(w1, 4) || misaligned(b1, 4) ||
+        misaligned(w2, 4) || misaligned(b2, 4) || misaligned(da, 4) || misaligned(dw1, 4) || misaligned(db1, 4) ||
+        misaligned(dw2, 4) || misaligned(db2, 4))
+        return fail(DG_E_ARG, "dg_embed_sym_bwd_bf16: misaligned pointer (g and workspace: 16 bytes)");
     if (B < 1 || !embed_bwd_bf16_ok(N, E, H, C, act))
         return fail(DG_E_SHAPE, "dg_embed_sym_bwd_bf16: unsupported B=%d N=%d E=%d H=%d C=%d act=%d (need N<=48, E<=8, H=64, "
                                 "C=128, relu or leaky)", B, N, E, H, C, act);

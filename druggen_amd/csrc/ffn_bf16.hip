@@ -655,6 +655,11 @@ extern "C" int dg_ffn_ln_fwd_bf16(const void* x, const void* packed, const float
                                   int64_t R, float eps, dg_stream_t stream_) {
     if (!x || !packed || !b1 || !b2 || !gamma || !beta || !y || !mean || !rstd)
         return fail(DG_E_ARG, "dg_ffn_ln_fwd_bf16: null pointer");      // pre, relu_bits: only needed for a backward
+    // 16-byte LDS-DMA of x, 16-byte fragment / parameter loads, 16-byte row stores
+    if (misaligned(x, 16) || misaligned(packed, 16) || misaligned(y, 16) || misaligned(pre, 16) || misaligned(b1, 16) ||
+        misaligned(b2, 16) || misaligned(gamma, 16) || misaligned(beta, 16) || misaligned(mean, 4) || misaligned(rstd, 4) ||
+        misaligned(relu_bits, 4))
+        return fail(DG_E_ARG, "dg_ffn_ln_fwd_bf16: misaligned pointer (rows, packed weights and parameters: 16 bytes)");
     if (R < 0) return fail(DG_E_SHAPE, "dg_ffn_ln_fwd_bf16: negative row count");
     if (R == 0) return 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -685,6 +690,12 @@ extern "C" int dg_ffn_ln_bwd_bf16(const void* x, const void* pre, const float* m
         return fail(DG_E_ARG, "dg_ffn_ln_bwd_bf16: null pointer");
     if (dw1 && (!dw2 || !db1 || !db2 || !bits_scratch))
         return fail(DG_E_ARG, "dg_ffn_ln_bwd_bf16: weight gradients need dw1, db1, dw2, db2 and bits_scratch together");
+    // 16-byte LDS-DMA of x and dz, 16-byte fragment / parameter loads, float4 partial sums and results
+    if (misaligned(x, 16) || misaligned(pre, 16) || misaligned(dy, 16) || misaligned(dz, 16) || misaligned(dx, 16) ||
+        misaligned(packed, 16) || misaligned(gamma, 16) || misaligned(b1, 4) || misaligned(workspace, 16) || misaligned(dw1, 16) ||
+        misaligned(dw2, 16) || misaligned(db1, 4) || misaligned(db2, 4) || misaligned(dgamma, 4) || misaligned(dbeta, 4) ||
+        misaligned(mean, 4) || misaligned(rstd, 4) || misaligned(relu_bits, 4) || misaligned(bits_scratch, 4))
+        return fail(DG_E_ARG, "dg_ffn_ln_bwd_bf16: misaligned pointer (rows, packed weights, gamma, workspace, dw1 / dw2: 16 bytes)");
     if (R < 1) return fail(DG_E_SHAPE, "dg_ffn_ln_bwd_bf16: empty input");
     if (workspace_bytes < dg_ffn_bf16_workspace_bytes(R)) return fail(DG_E_WORKSPACE, "dg_ffn_ln_bwd_bf16: workspace too small");
     hipStream_t stream = static_cast<hipStream_t>(stream_);

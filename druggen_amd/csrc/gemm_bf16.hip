@@ -247,6 +247,11 @@ int row_gemm_bf16(const bf16_t* a, const void* packed, bf16_t* y, int64_t R, int
         return fail(DG_E_SHAPE, "dg_row_gemm(bf16): unsupported K=%d N=%d (supported: 128x128, 128x384, 384x128)", K, N);
     if (gamma && (N != 128 || !beta || !mean || !rstd))
         return fail(DG_E_ARG, "dg_row_gemm: LayerNorm epilogue needs N == 128, beta, mean and rstd");
+    // 16-byte LDS-DMA of the rows, 16-byte fragment / parameter loads, 8-byte row stores at multiples of 8 bytes from the base
+    if (misaligned(a, 16) || misaligned(packed, 16) || misaligned(y, 16) || misaligned(residual, 16) || misaligned(pre_ln, 16) ||
+        misaligned(bias, 16) || misaligned(gamma, 16) || misaligned(beta, 16) || misaligned(mean, 4) || misaligned(rstd, 4) ||
+        misaligned(relu_bits_out, 4) || misaligned(mask_bits, 4))
+        return fail(DG_E_ARG, "dg_row_gemm(bf16): misaligned pointer (rows, packed weights and parameters: 16 bytes)");
     if (R == 0) return 0;
     EpiB ep{bias, mask_bits, relu_bits_out, residual, gamma, beta, mean, rstd, pre_ln, eps, relu};
     const int64_t tiles = (R + kRowsPerTile - 1) / kRowsPerTile;

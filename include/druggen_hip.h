@@ -306,7 +306,9 @@ int dg_launch_pair_end(dg_stream_t stream);
  * input-gradient launch of the NEXT layer (same R, K, N geometry) takes it as
  * mask_bits and zeroes the masked outputs (reference: threshold_backward of
  * layers.py:51).  LayerNorm epilogue (gamma != NULL; layers.py:187-192) needs
- * N == 128, writes mean/rstd [R] and, if pre_ln != NULL, the pre-LayerNorm sum.   */
+ * N == 128, writes mean/rstd [R] and, if pre_ln != NULL, the pre-LayerNorm sum.
+ * DG_DTYPE_BF16: a, packed, y, residual, pre_ln, bias, gamma and beta must be 16-byte aligned (the rows arrive by 16-byte
+ * LDS-DMA), the other pointers 4-byte aligned; a misaligned pointer: DG_E_ARG before any launch.   */
 size_t dg_row_gemm_packed_bytes(int n_out, int k_contract, int dtype);
 int dg_row_gemm_pack(const float* w, void* packed, int rows, int cols, int mode, int dtype, dg_stream_t stream);
 /* Many packs in one launch (after an optimizer step every weight of the network is stale at once): `table` is a DEVICE
@@ -440,7 +442,10 @@ int dg_edge_ffn_ln_bwd_pair(const dg_ffn_bwd_args* node, const dg_ffn_bwd_args* 
  * _bwd: dy [R,128] -> dz [R,128] (scratch the caller owns: LayerNorm input gradient, bf16), dx (nullable),
  * dgamma, dbeta, and -- when dw1 != NULL -- dw1 [384,128], db1, dw2 [128,384], db2 (float32);
  * bits_scratch: dg_ffn_bf16_mask_words(R) words of scratch, needed with the weight gradients.
- * First order only: the gradient penalty's twice-differentiated pass uses dg_edge_ffn_ln_fwd/_bwd.   */
+ * First order only: the gradient penalty's twice-differentiated pass uses dg_edge_ffn_ln_fwd/_bwd.
+ * Row tensors (x, y, pre_ln, dy, dz, dx), packed, the workspace, dw1 / dw2 and the parameter vectors read as float4 (b1, b2,
+ * gamma, beta of _fwd; gamma of _bwd) must be 16-byte aligned (16-byte LDS-DMA and vector accesses); every other pointer,
+ * b1 of _bwd (read as scalars) included, 4-byte aligned; a misaligned one: DG_E_ARG, no launch.   */
 int64_t dg_ffn_bf16_padded_rows(int64_t R);     /* rows y / pre_ln / mean / rstd of _fwd must hold (R rounded up to whole tiles) */
 size_t dg_ffn_bf16_packed_bytes(void);
 int dg_ffn_bf16_pack(const float* w1, const float* w2, void* packed, dg_stream_t stream);
@@ -497,7 +502,8 @@ int dg_embed_sym_bwd(const float* a, const float* w1, const float* b1, const flo
 /* The same backward for bf16 gradients `g` and the piecewise-linear activations (act 0 = relu, 1 = leaky), E <= 8: whole
  * row blocks g[b,i,:,:] and g[b,:,i,:] stream through LDS, one bf16 MFMA per product (the bf16 configuration's
  * arithmetic), fp32 accumulation -- ~5x faster than dg_embed_sym_bwd at configs[2].  w2 is the RAW [C,H] float32
- * parameter (fragments are built in the kernel); da may be NULL.                                                   */
+ * parameter (fragments are built in the kernel); da may be NULL.  g and the workspace must be 16-byte aligned (16-byte
+ * LDS-DMA of the gradient rows), the float32 pointers 4-byte aligned; a misaligned one: DG_E_ARG before any launch.   */
 size_t dg_embed_sym_bwd_bf16_workspace_bytes(int B, int N);
 int dg_embed_sym_bwd_bf16(const float* a, const float* w1, const float* b1, const float* w2, const float* b2,
                           const void* g, float* da, float* dw1, float* db1, float* dw2, float* db2,
