@@ -173,6 +173,11 @@ DESC_SIGNATURES = {
     "dg_mol_descriptors": (c_int, [_P] * 9 + [c_int] + [_P] * 2 + [c_int, _P] + [c_int] * 5 + [_P] * 3 + [_P]),
 }
 
+# ... and for include/druggen_hip_sub.h
+SUB_SIGNATURES = {
+    "dg_mol_substructure": (c_int, [_P] * 7 + [c_int, _P, c_int, _P] + [c_int] * 4 + [_P] * 3 + [_P]),
+}
+
 KERNEL_IDS = {"attn_fwd": 0, "attn_bwd": 1, "attn_bwd2": 2, "ln_fwd": 3, "ln_bwd": 4, "ln_bwd2": 5, "linear_wgrad": 6, "row_gemm": 7, "embed_sym": 8, "ffn": 9, "ffn_wgrad": 10,
               "attn_half_fwd": 11, "attn_half_bwd": 12,
               "row_gemm_e128": 13, "row_gemm_e_n384": 14, "row_gemm_e_k384": 15,
@@ -218,7 +223,8 @@ def load() -> ctypes.CDLL:
                 f"{LIB_PATH} not found: build it with `python -m druggen_amd.build` "
                 "(druggen_amd has no CPU / eager fallback)")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**SIGNATURES, **TEXT_SIGNATURES, **FP_SIGNATURES, **VALID_SIGNATURES, **DESC_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **TEXT_SIGNATURES, **FP_SIGNATURES, **VALID_SIGNATURES, **DESC_SIGNATURES,
+                                   **SUB_SIGNATURES}.items():
             fn = getattr(lib, name)   # AttributeError if the .so lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = lib

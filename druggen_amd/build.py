@@ -3,8 +3,8 @@
     python -m druggen_amd.build            # rebuild if sources are newer
     python -m druggen_amd.build --force
 The shared object has no PyTorch / pybind dependency: it is the C ABI declared
-in include/druggen_hip.h, include/druggen_hip_text.h, include/druggen_hip_fp.h, include/druggen_hip_valid.h and
-include/druggen_hip_desc.h and is loaded with ctypes (druggen_amd/_lib.py).
+in include/druggen_hip.h, include/druggen_hip_text.h, include/druggen_hip_fp.h, include/druggen_hip_valid.h,
+include/druggen_hip_desc.h and include/druggen_hip_sub.h and is loaded with ctypes (druggen_amd/_lib.py).
 """
 from __future__ import annotations
 
@@ -23,6 +23,8 @@ HEADERS = [os.path.join(INCLUDE, "druggen_hip.h"), os.path.join(INCLUDE, "drugge
            os.path.join(INCLUDE, "druggen_hip_fp.h"), os.path.join(INCLUDE, "druggen_hip_valid.h")]
 # the fifth header, beside the list: tests/test_mol_valid_host.py pins HEADERS to the four above
 DESC_HEADER = os.path.join(INCLUDE, "druggen_hip_desc.h")
+# ... and the sixth
+SUB_HEADER = os.path.join(INCLUDE, "druggen_hip_sub.h")
 ARCH = "gfx950"
 
 
@@ -34,7 +36,7 @@ def _stale() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + HEADERS + [DESC_HEADER]
+    deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + HEADERS + [DESC_HEADER, SUB_HEADER]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -46,7 +48,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         raise RuntimeError("hipcc not found: cannot build libdruggen_hip.so")
     os.makedirs(LIB_DIR, exist_ok=True)
     objs, jobs = [], []
-    headers = glob.glob(os.path.join(CSRC, "*.h")) + HEADERS + [DESC_HEADER]
+    headers = glob.glob(os.path.join(CSRC, "*.h")) + HEADERS + [DESC_HEADER, SUB_HEADER]
     for src in sources():
         obj = os.path.join(LIB_DIR, os.path.basename(src) + ".o")
         objs.append(obj)

@@ -56,10 +56,12 @@ class MoleculeBatch(PackedRecord):
     On the device the fields are ``torch`` tensors.  ``cpu()`` moves the packed buffer with ONE device->host copy and
     returns a host batch whose fields are ``numpy`` views of it; ``edge_list`` / ``edge_labels`` / ``truncated`` work on
     the host batch.  ``validity``: the ``validity.MoleculeValidity`` of a batch sampled by ``MoleculeSampler(..., validity=)``,
-    else None; ``descriptors``: the ``descriptors.MoleculeDescriptors`` of one sampled with ``descriptors=`` too, else None."""
+    else None; ``descriptors``: the ``descriptors.MoleculeDescriptors`` of one sampled with ``descriptors=`` too, else None;
+    ``matches``: the ``substructure.MoleculeMatches`` of one sampled with ``substructures=`` as well, else None."""
 
     validity = None
     descriptors = None
+    matches = None
 
     def __init__(self, buffer, B, N, cap, with_valence):
         self.B, self.N, self.cap = B, N, cap

@@ -15,6 +15,7 @@ from .functional import (activation_dtype, as_one_hot, attach_one_hot_labels, bu
 from .smiles_out import SmilesTables, write_smiles
 from .validity import ValenceTables, check_molecules
 from .descriptors import DescriptorTables, describe_molecules
+from .substructure import SubstructureTables, match_molecules
 
 __all__ = ["MoleculeSampler"]
 
@@ -47,10 +48,16 @@ class MoleculeSampler:
     ``descriptors``: ``descriptors.DescriptorTables`` on the batch's device, together with ``validity=`` (``ValueError``
     without it: the descriptors are made of the verdicts) -- every sample then also describes each molecule's largest fragment
     (``descriptors.describe_molecules``: one more launch behind the check, inside the captured graph when there is one); the
-    ``MoleculeDescriptors`` is ``batch.descriptors`` and ``sampler.descriptors``.  None: both stay None."""
+    ``MoleculeDescriptors`` is ``batch.descriptors`` and ``sampler.descriptors``.  None: both stay None.
+
+    ``substructures``: ``substructure.SubstructureTables`` on the batch's device, together with ``validity=`` and
+    ``descriptors=`` (``ValueError`` without them: the matcher reads the descriptors' keys and bond classes) -- every sample then
+    also matches the tables' patterns (``substructure.match_molecules``: one more launch behind the descriptors, inside the
+    captured graph when there is one); the ``MoleculeMatches`` is ``batch.matches`` and ``sampler.matches``.  None: both stay
+    None."""
 
     def __init__(self, G, edge, node, *, graph: bool = True, bond_order2=None, bond_cap=None, warmup: int = 3, smiles=None,
-                 validity=None, descriptors=None):
+                 validity=None, descriptors=None, substructures=None):
         if not (edge.is_cuda and node.is_cuda):
             raise RuntimeError("druggen_amd.sampling runs on the GPU (no CPU fallback)")
         if smiles is not None and not isinstance(smiles, SmilesTables):
@@ -61,10 +68,16 @@ class MoleculeSampler:
             raise TypeError("descriptors= takes descriptors.DescriptorTables (DescriptorTables.from_decoders)")
         if descriptors is not None and validity is None:
             raise ValueError("descriptors= needs validity= as well: the descriptors are made of the validity check's verdicts")
+        if substructures is not None and not isinstance(substructures, SubstructureTables):
+            raise TypeError("substructures= takes substructure.SubstructureTables (SubstructureTables.from_decoders)")
+        if substructures is not None and (validity is None or descriptors is None):
+            raise ValueError("substructures= needs validity= and descriptors= as well: the matcher reads the descriptors' atom "
+                             "keys and bond classes")
         self.G = G
         self.smiles_tables, self.smiles = smiles, None
         self.validity_tables, self.validity = validity, None
         self.descriptor_tables, self.descriptors = descriptors, None
+        self.substructure_tables, self.matches = substructures, None
         self.bond_cap = bond_cap
         self._order2 = _order2_table(bond_order2, edge.shape[-1], node.device)      # on the device before any capture
         self.graph = None
@@ -113,6 +126,8 @@ class MoleculeSampler:
                     self.validity = batch.validity = check_molecules(batch, self.validity_tables)
                 if self.descriptor_tables is not None:
                     self.descriptors = batch.descriptors = describe_molecules(batch, batch.validity, self.descriptor_tables)
+                if self.substructure_tables is not None:
+                    self.matches = batch.matches = match_molecules(batch, batch.descriptors, self.substructure_tables)
         finally:
             for m, was in modes:
                 m.training = was
