@@ -4,7 +4,7 @@
     python -m druggen_amd.build --force
 The shared object has no PyTorch / pybind dependency: it is the C ABI declared
 in include/druggen_hip.h, include/druggen_hip_text.h, include/druggen_hip_fp.h, include/druggen_hip_valid.h,
-include/druggen_hip_desc.h and include/druggen_hip_sub.h and is loaded with ctypes (druggen_amd/_lib.py).
+include/druggen_hip_desc.h, include/druggen_hip_sub.h and include/druggen_hip_scaf.h and is loaded with ctypes (druggen_amd/_lib.py).
 """
 from __future__ import annotations
 
@@ -25,6 +25,8 @@ HEADERS = [os.path.join(INCLUDE, "druggen_hip.h"), os.path.join(INCLUDE, "drugge
 DESC_HEADER = os.path.join(INCLUDE, "druggen_hip_desc.h")
 # ... and the sixth
 SUB_HEADER = os.path.join(INCLUDE, "druggen_hip_sub.h")
+# ... and the seventh
+SCAF_HEADER = os.path.join(INCLUDE, "druggen_hip_scaf.h")
 ARCH = "gfx950"
 
 
@@ -36,7 +38,7 @@ def _stale() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + HEADERS + [DESC_HEADER, SUB_HEADER]
+    deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + HEADERS + [DESC_HEADER, SUB_HEADER, SCAF_HEADER]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -48,7 +50,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         raise RuntimeError("hipcc not found: cannot build libdruggen_hip.so")
     os.makedirs(LIB_DIR, exist_ok=True)
     objs, jobs = [], []
-    headers = glob.glob(os.path.join(CSRC, "*.h")) + HEADERS + [DESC_HEADER, SUB_HEADER]
+    headers = glob.glob(os.path.join(CSRC, "*.h")) + HEADERS + [DESC_HEADER, SUB_HEADER, SCAF_HEADER]
     for src in sources():
         obj = os.path.join(LIB_DIR, os.path.basename(src) + ".o")
         objs.append(obj)

@@ -57,11 +57,13 @@ class MoleculeBatch(PackedRecord):
     returns a host batch whose fields are ``numpy`` views of it; ``edge_list`` / ``edge_labels`` / ``truncated`` work on
     the host batch.  ``validity``: the ``validity.MoleculeValidity`` of a batch sampled by ``MoleculeSampler(..., validity=)``,
     else None; ``descriptors``: the ``descriptors.MoleculeDescriptors`` of one sampled with ``descriptors=`` too, else None;
-    ``matches``: the ``substructure.MoleculeMatches`` of one sampled with ``substructures=`` as well, else None."""
+    ``matches``: the ``substructure.MoleculeMatches`` of one sampled with ``substructures=`` as well, else None; ``scaffolds``: the
+    ``scaffolds.MoleculeScaffolds`` of one sampled with ``scaffolds=True``, else None."""
 
     validity = None
     descriptors = None
     matches = None
+    scaffolds = None
 
     def __init__(self, buffer, B, N, cap, with_valence):
         self.B, self.N, self.cap = B, N, cap

@@ -16,6 +16,7 @@ from .smiles_out import SmilesTables, write_smiles
 from .validity import ValenceTables, check_molecules
 from .descriptors import DescriptorTables, describe_molecules
 from .substructure import SubstructureTables, match_molecules
+from .scaffolds import murcko_scaffolds
 
 __all__ = ["MoleculeSampler"]
 
@@ -54,10 +55,15 @@ class MoleculeSampler:
     ``descriptors=`` (``ValueError`` without them: the matcher reads the descriptors' keys and bond classes) -- every sample then
     also matches the tables' patterns (``substructure.match_molecules``: one more launch behind the descriptors, inside the
     captured graph when there is one); the ``MoleculeMatches`` is ``batch.matches`` and ``sampler.matches``.  None: both stay
-    None."""
+    None.
+
+    ``scaffolds``: True, together with ``validity=`` and ``descriptors=`` (``ValueError`` without them: the scaffolds are cut
+    along the descriptors' bond classes, with the descriptor tables' bond table) -- every sample then also cuts out each
+    molecule's scaffold (``scaffolds.murcko_scaffolds``: one more launch behind the descriptors, inside the captured graph when
+    there is one); the ``MoleculeScaffolds`` is ``batch.scaffolds`` and ``sampler.scaffolds``.  False: both stay None."""
 
     def __init__(self, G, edge, node, *, graph: bool = True, bond_order2=None, bond_cap=None, warmup: int = 3, smiles=None,
-                 validity=None, descriptors=None, substructures=None):
+                 validity=None, descriptors=None, substructures=None, scaffolds=False):
         if not (edge.is_cuda and node.is_cuda):
             raise RuntimeError("druggen_amd.sampling runs on the GPU (no CPU fallback)")
         if smiles is not None and not isinstance(smiles, SmilesTables):
@@ -73,11 +79,15 @@ class MoleculeSampler:
         if substructures is not None and (validity is None or descriptors is None):
             raise ValueError("substructures= needs validity= and descriptors= as well: the matcher reads the descriptors' atom "
                              "keys and bond classes")
+        if scaffolds and (validity is None or descriptors is None):
+            raise ValueError("scaffolds=True needs validity= and descriptors= as well: the scaffolds are cut along the "
+                             "descriptors' atom keys and bond classes")
         self.G = G
         self.smiles_tables, self.smiles = smiles, None
         self.validity_tables, self.validity = validity, None
         self.descriptor_tables, self.descriptors = descriptors, None
         self.substructure_tables, self.matches = substructures, None
+        self.with_scaffolds, self.scaffolds = bool(scaffolds), None
         self.bond_cap = bond_cap
         self._order2 = _order2_table(bond_order2, edge.shape[-1], node.device)      # on the device before any capture
         self.graph = None
@@ -128,6 +138,8 @@ class MoleculeSampler:
                     self.descriptors = batch.descriptors = describe_molecules(batch, batch.validity, self.descriptor_tables)
                 if self.substructure_tables is not None:
                     self.matches = batch.matches = match_molecules(batch, batch.descriptors, self.substructure_tables)
+                if self.with_scaffolds:
+                    self.scaffolds = batch.scaffolds = murcko_scaffolds(batch, batch.descriptors, self.descriptor_tables)
         finally:
             for m, was in modes:
                 m.training = was
